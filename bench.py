@@ -2,7 +2,7 @@
 """Headline benchmark: sec / IPM-iteration of the TT-IPM Newton/KKT path on maxcut dim=10 rank=1
 (BASELINE.json `metric`, config `configs/maxcut_10.yaml`), seed-sharded over N GPUs.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -29,18 +29,27 @@
   columns unequal.
 * Timed region: barrier + device sync on both sides of the K steps, max over ranks.
   `value` = (max-over-ranks wall) / (IPM iterations of all ranks): whole-job s per IPM-iteration.
-* `sec_per_iter_per_seed_median`: SURVEY.md §8(d)'s statistic as the reference runner measures it
+  `ms_per_step` = that wall / K.
+* A plain run is set-up, warm-up, the K timed steps and the result line, nothing else.  `--full`
+  adds the three untimed legs below (the one-at-a-time latency pass, `roofline`, `cpu_baseline`;
+  `--no-solo`, `--no-roofline` and `--no-cpu-baseline` take them out again one by one); without it
+  their keys of the line are null.
+* `--dump-outputs DIR` (after the timed steps, outside the timed region): what each solve of the last
+  timed step returned to its caller, as DIR/<name>.npy in float64, one row per solve ordered by
+  (rank, slot): `seed`, `num_iters`, `gap`, `feas`, `dual_feas`, `ranksX/Y/Z/T` (`last_step_outputs`).
+  The same arguments give the same seeds, problems and RNG states, row for row.
+* `--full`, `sec_per_iter_per_seed_median`: SURVEY.md §8(d)'s statistic as the reference runner measures it
   (`src/utils.py:298-302`: one solve at a time, solve wall / its IPM iterations, median over seeds):
   after the timed region (rank 0, N=1) every distinct timed seed is solved once more ALONE on the
   GPU.  `sec_per_iter_per_seed_median_inflight` is the same statistic over the timed (contended)
   solves.
-* `roofline` (contraction kernels: the MFMA GEMM `gemm_offs*`, the fused local apply and the Schur
+* `--full`, `roofline` (contraction kernels: the MFMA GEMM `gemm_offs*`, the fused local apply and the Schur
   multi-task apply): an untimed re-solve of each distinct seed rank 0 timed (the timed region's seed
   mix) with every contraction launch bracketed by HIP events on its stream.  achieved = ALGORITHMIC contraction FLOPs of that solve
   (NumPy `einsum_path` greedy convention per einsum call plus the chained applies of every local
   KKT operator application; `dev.ALGO`) / summed contraction kernel time; peak =
   78.6 TFLOP/s fp64 matrix.
-* `cpu_baseline` (rank 0, N=1 only): the oracle CPU restatement of the reference path (`oracle/`,
+* `--full`, `cpu_baseline` (rank 0, N=1 only): the oracle CPU restatement of the reference path (`oracle/`,
   a port) on this host: one single-thread process per distinct timed seed, all at once, each its
   seed's WHOLE solve (`--cpu-cap` is only a safety bound).  `value` = median over seeds of solve
   wall / IPM iterations; beside it the GPU's one-at-a-time figure for the same seeds, as a ratio of
@@ -279,8 +288,9 @@ class _Slots:
             if device is not None:
                 torch.cuda.current_stream().synchronize()
             elapsed = time.perf_counter() - t0
-            for r, tr in zip(res, traces):  # per-iteration stamps (Newton-system assemblies)
+            for k, (r, tr) in enumerate(zip(res, traces)):  # per-iteration stamps (Newton-system assemblies)
                 r["assembly_t"] = [e["t"] - tr[0]["t"] for e in tr] if tr else []
+                r["slot"], r["nth"] = self.slot_base + j, k  # the slot that solved it, and its place among that slot's solves
             self.out[j] = (elapsed, res)
         except BaseException as e:  # noqa: BLE001
             self.err.append(e)
@@ -329,7 +339,8 @@ def _gpu_worker(args, slot_seeds, queue=None):
     from ttipm_amd.utils import create
     from ttipm_amd.utils import solve as _solve
     config = yaml.safe_load(open(args.config))
-    keep = ("seed", "num_iters", "runtime", "sec_per_iter", "gap", "feas", "dual_feas", "assembly_t")
+    keep = ("seed", "num_iters", "runtime", "sec_per_iter", "gap", "feas", "dual_feas", "assembly_t",
+            "ranksX", "ranksY", "ranksZ", "ranksT", "slot", "nth")
     with contextlib.redirect_stdout(sys.stderr):  # once, around all slot threads (not thread-safe)
         need = [s for sl in slot_seeds for s in sl] + (list(queue[0]) if queue else [])
         packed = {s: shard.pack(create(args.problem, config, s, args.rank, verbose=False)) for s in dict.fromkeys(need)}
@@ -542,6 +553,38 @@ def cpu_summary(per, allc, gpu_runs, cap, workload, cores_avail, ref_iters=None)
             "per_seed": rows}
 
 
+OUTPUT_SCALARS = ("seed", "num_iters", "gap", "feas", "dual_feas")
+OUTPUT_RANKS = ("ranksX", "ranksY", "ranksZ", "ranksT")
+
+
+def last_step_outputs(all_results):
+    """What the last timed step computed, as float64 arrays: one row per solve of that step (each
+    slot's last solve), ordered by (rank, slot).  The columns are what `ttipm_amd.utils.solve`, the
+    timed call, hands its caller: the seed, the IPM iteration count, the recorded duality gap and
+    squared primal / dual feasibility residuals of the end point, and its TT ranks (X, Y, Z, T).
+    The seeds of a step follow from the arguments alone (`make_schedule`) and each solve starts from
+    its seed's problem and MT19937 state, so two runs with the same arguments solve identical inputs
+    row for row.  (`--balance dynamic` hands the solves out first come first served: there a row is
+    whatever its slot solved last.)"""
+    last = {}
+    for r in all_results:
+        key = (r.get("rank", 0), r["slot"])
+        if key not in last or r["nth"] > last[key]["nth"]:
+            last[key] = r
+    rows = [last[k] for k in sorted(last)]
+    out = {k: np.array([r[k] for r in rows], dtype=np.float64) for k in OUTPUT_SCALARS}
+    for k in OUTPUT_RANKS:
+        out[k] = np.array([r[k] for r in rows], dtype=np.float64).reshape(len(rows), -1)
+    return out
+
+
+def dump_outputs(path, all_results):
+    """`--dump-outputs DIR`: `last_step_outputs` as DIR/<name>.npy (a few hundred bytes each)."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in last_step_outputs(all_results).items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 LINE_MAX = 4000  # the driver keeps a ~14.8 KB tail of stdout; the line stays far below it
 
 
@@ -595,6 +638,18 @@ def compose_line(problem, config, cfg_name, rank_tt, world, P, T, n_procs, steps
     return line, detail
 
 
+def write_detail(path, detail, line):
+    """The `--detail` side file.  Where it cannot be written (a read-only tree, say) the run and its
+    line still stand: the reason goes to stderr and the line's `detail` becomes null."""
+    try:
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            json.dump(detail, f, indent=1)
+    except OSError as e:
+        print(f"bench: detail file not written: {e}", file=sys.stderr)
+        line["detail"] = None
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--gpus", type=int, default=1)
@@ -609,9 +664,16 @@ def main():
                          "maxcut_10 seed's whole solve on the GPU box's host")
     ap.add_argument("--detail", default=os.path.join("gpurun_out", "bench_detail.json"),
                     help="side file for the per-seed / per-step / per-op detail ('' to skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-solo", action="store_true", help="skip the one-solve-at-a-time latency pass")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the one-solve-at-a-time latency pass, the roofline "
+                         "re-solves and the CPU baseline (each can be switched off below); without it the run is "
+                         "set-up, warm-up, the timed steps and the result line only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step's solves returned as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline re-solves")
+    ap.add_argument("--no-solo", action="store_true",
+                    help="with --full: skip the one-solve-at-a-time latency pass")
     ap.add_argument("--schedule", choices=("shard", "replica"), default="shard")
     ap.add_argument("--threads", type=int, default=None,
                     help="solves in flight per process (host threads; default: default_threads())")
@@ -638,6 +700,8 @@ def main():
         if args.queue_file:
             q = ([int(x) for x in args.queue_work.split(",")], args.queue_file)
         return _gpu_worker(args, [[int(x) for x in sl.split(",")] for sl in args.gpu_worker.split(";")], q)
+    if not args.full:  # a plain run: nothing but what `value` needs
+        args.no_cpu_baseline = args.no_roofline = args.no_solo = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -757,6 +821,8 @@ def main():
     slot_elapsed = slot_elapsed + [e for w in worker_out for e in w["elapsed"]]
     results = results + [r for w in worker_out for r in w["results"]]
     iters = sum(r["num_iters"] for r in results)
+    for r in results:
+        r["rank"] = rank
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if torch.cuda.is_available() else "cpu")
         n = torch.tensor([float(iters)], dtype=torch.float64, device=t.device)
@@ -764,6 +830,8 @@ def main():
         dist.all_reduce(n, op=dist.ReduceOp.SUM)
         elapsed, iters = float(t.item()), int(n.item())
     all_results = shard.gather_results(results)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, all_results)
 
     roofline = None
     if not args.no_roofline and rank == 0:
@@ -834,9 +902,7 @@ def main():
             all_results=all_results, solo=solo, roofline=roofline, cpu=cpu, detail_path=args.detail,
             balance=args.balance)
         if args.detail:
-            os.makedirs(os.path.dirname(os.path.abspath(args.detail)), exist_ok=True)
-            with open(args.detail, "w") as f:
-                json.dump(detail, f, indent=1)
+            write_detail(args.detail, detail, line)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

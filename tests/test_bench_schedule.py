@@ -4,6 +4,7 @@ import json
 import os
 import sys
 
+import numpy as np
 import pytest
 import yaml
 
@@ -160,3 +161,37 @@ def test_dynamic_balance_claims_every_solve_once(tmp_path):
     for p in procs:
         p.join(timeout=60)
     assert sorted(got) == list(range(n))
+
+
+def test_dump_outputs_writes_the_last_step(tmp_path):
+    """`--dump-outputs`: one float64 row per solve of the last timed step, ordered by (rank, slot),
+    whatever order the processes' results arrive in; the files are the solve's returned values."""
+    P, K = 4, 3
+    _, sched, _ = bench.make_schedule(_cfg("maxcut_10.yaml"), "maxcut_10.yaml", None, K, 1, 0, P, "shard")
+    res = []
+    for j in (2, 0, 3, 1):  # slot-major, as the processes report, in a scrambled process order
+        for k in range(K):
+            res.append({"seed": sched[k][j], "num_iters": 10 + j + k, "gap": 1e-4 * (j + 1) + k, "feas": 1e-7 * (k + 1),
+                        "dual_feas": 1e-10 * (j + 1), "ranksX": [2 + j] * 9, "ranksY": [1] * 9, "ranksZ": [3] * 9,
+                        "ranksT": [0] * 9, "rank": 0, "slot": j, "nth": k, "runtime": 1.0})
+    bench.dump_outputs(str(tmp_path / "out"), res)
+    got = {f[:-4]: np.load(tmp_path / "out" / f) for f in sorted(os.listdir(tmp_path / "out"))}
+    assert set(got) == set(bench.OUTPUT_SCALARS + bench.OUTPUT_RANKS)
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["seed"].tolist() == sched[-1]
+    assert got["num_iters"].tolist() == [10 + j + K - 1 for j in range(P)]
+    assert got["gap"].tolist() == [1e-4 * (j + 1) + K - 1 for j in range(P)]
+    assert got["ranksX"].shape == (P, 9) and got["ranksX"][:, 0].tolist() == [2.0, 3.0, 4.0, 5.0]
+    assert sum(a.nbytes for a in got.values()) < 64 << 20
+
+
+def test_detail_file_is_best_effort(tmp_path, capsys):
+    """The `--detail` side file: written where it can be; where it cannot (here: its folder's name is
+    taken by a file), the run goes on and the line says that there is no detail file."""
+    line = {"value": 1.0, "detail": str(tmp_path / "d" / "detail.json")}
+    bench.write_detail(line["detail"], {"line": line, "per_seed": []}, line)
+    assert json.load(open(tmp_path / "d" / "detail.json"))["line"]["value"] == 1.0
+    (tmp_path / "f").write_text("")
+    line["detail"] = str(tmp_path / "f" / "detail.json")
+    bench.write_detail(line["detail"], {"line": line}, line)
+    assert line["detail"] is None and "detail file not written" in capsys.readouterr().err

@@ -1,6 +1,6 @@
 # Whole-job bench under bit-identical knob variants, alternating with the defaults on one box.
 #   bash tools/ab_knobs.sh "TTK_SPLITK_FUSED=0" "TTK_ARNOLDI_ONE=0" ...   [BENCH_ARGS env: extra bench.py args;
-#   SOLO=" " also runs the one-solve-at-a-time pass (per-seed median)]
+#   SOLO="--full" also runs the one-solve-at-a-time pass (per-seed median)]
 set -o pipefail
 for i in 1 2; do
   for v in "DEFAULT=1" "$@"; do
