@@ -517,6 +517,28 @@ int ttk_zipup(ttk_ctx ctx, int kind, int d, const double *const *a, const int64_
               const double *const *b, const int64_t *b_ranks, const int64_t *modes, double eps,
               double *const *out, int64_t *out_ranks);
 
+/* Randomised fixed-rank TT rounding in one launch (`_tt_lr_random_orthogonalise`, src/tt_ops.py:
+ * 89-101, with the sketch contractions of `tt_rl_contraction`, src/tt_ops.py:51-58): one workgroup
+ * first walks right to left, W_k = unfold(A_k W_{k+1}) unfold(B_k)^T for the train A and the sketch B
+ * (kept in one stream-ordered scratch block), then left to right: Y = Z W_{i+1}, economic Householder
+ * QR of Y (LAPACK's sign convention; m < n handled), core i <- Q, core i+1 <- (Q^T Z) core_{i+1}, the
+ * carried core staying in LDS.  No SVD, no truncation decision and no host read: the output ranks are
+ * host arithmetic, out_ranks[0] = ranks[0], out_ranks[i+1] = min(out_ranks[i] inner[i],
+ * sketch_ranks[i+1]) (they may grow where a target exceeds the input rank), and the call returns
+ * after enqueueing.  Fixed summation order: two calls on the same input give the same bits.
+ * cores[k]: device, contiguous (ranks[k], inner[k], ranks[k+1]) fp64, read only; sketch[k]
+ * likewise with sketch_ranks (sketch[0] is never read; ranks[d] == sketch_ranks[d]); out[k]:
+ * caller-owned contiguous buffers of out_ranks[k] inner[k] out_ranks[k+1] doubles that overlap no
+ * input; ranks, sketch_ranks, out_ranks: d+1 entries.  ttk_rand_orth_lds: the bytes of LDS the sweep
+ * needs, or -1 when the train does not fit one workgroup (at most 160 KiB and 32 cores) or the
+ * arguments are invalid -- the caller then composes the sweep from ttk_einsum and ttk_qr.
+ * ttk_rand_orth validates on the host (d >= 2, every rank and extent >= 1, the LDS fit) and returns
+ * TTK_ERR_ARG without launching when a check fails. */
+int64_t ttk_rand_orth_lds(int d, const int64_t *inner, const int64_t *ranks, const int64_t *sketch_ranks);
+int ttk_rand_orth(ttk_ctx ctx, int d, const double *const *cores, const int64_t *inner, const int64_t *ranks,
+                  const double *const *sketch, const int64_t *sketch_ranks, double *const *out,
+                  int64_t *out_ranks);
+
 /* Dense Schur-complement local KKT solve in one call (SURVEY §8(b) `ttk_local_assemble` +
  * `ttk_dense_schur_solve`; the dense branch of `_ipm_local_solver`, src/tt_ipm.py:183-229):
  * assembles L_XI = B22 diag(inv_I), L_eq = B01, L_Z = B21 (each 'lsr,smnS,LSR->lmLrnR'), Cholesky of

@@ -417,6 +417,151 @@ def tt_rank_retraction(tt, upper_ranks):
     return tt
 
 
+# ------------------------------------------------------------------ randomised rounding (`src/tt_ops.py:51-101`)
+def tt_rl_contraction(a, b):
+    """`src/tt_ops.py:51-58`: the d-1 partial contractions of two trains from the right, W_k of shape
+    (ra_k, rb_k) for the bonds k = 1..d-1: W_{d-1} = A_{d-1} B_{d-1}^T on the (r, inner) unfoldings, then
+    W_k = unfold(A_k W_{k+1}) unfold(B_k)^T."""
+    ra, rb = a[-1].shape[0], b[-1].shape[0]
+    out = [D.einsum("ik,jk->ij", D.contig(a[-1]).view(ra, -1), D.contig(b[-1]).view(rb, -1))]
+    for ca, cb in zip(a[-2:0:-1], b[-2:0:-1]):
+        w = out[-1]
+        z = D.matmul(D.contig(ca).view(-1, w.shape[0]), w)
+        out.append(D.einsum("ik,jk->ij", z.view(ca.shape[0], -1), D.contig(cb).view(cb.shape[0], -1)))
+    return out[::-1]
+
+
+def tt_lr_contraction(a, b):
+    """`src/tt_ops.py:61-65`: `tt_rl_contraction` of the mirrored trains."""
+    return tt_swap_all(tt_rl_contraction(tt_swap_all(a), tt_swap_all(b)))
+
+
+def randorth_ranks(r0, inner, sketch_ranks):
+    """Bond ranks [r'_0, ..., r'_{d-1}] that `_tt_lr_random_orthogonalise` gives a train with leading
+    rank r0 and middle extents `inner` (d entries) under a sketch with bond ranks `sketch_ranks` (d-1
+    entries): r'_0 = r0, r'_{i+1} = min(r'_i * inner_i, l_{i+1}) -- the column count of the economic QR
+    of the (r'_i inner_i, l_{i+1}) sketched unfolding.  Host arithmetic only; a rank grows where the
+    target exceeds it."""
+    out = [int(r0)]
+    for n, l in zip(inner, sketch_ranks):
+        out.append(min(out[-1] * int(n), int(l)))
+    return out
+
+
+NATIVE_RANDORTH = os.environ.get("TTIPM_NATIVE_RANDORTH", "1") == "1"
+
+
+def _inner(c):
+    return int(np.prod(c.shape[1:-1])) if c.dim() > 2 else 1
+
+
+def _randorth_composed(tt, gs):
+    """The sweep from D.einsum / D.matmul / D.qr (3 launches and a QR per bond); also what a train too
+    large for `ttk_rand_orth` takes."""
+    d = len(tt)
+    W = tt_rl_contraction(tt, gs)
+    rk = randorth_ranks(tt[0].shape[0], [_inner(c) for c in tt[:-1]], [w.shape[1] for w in W])
+    out = [None] * d
+    cur = D.contig(tt[0])
+    for i, w in enumerate(W):
+        nsh = tt[i + 1].shape
+        Z = cur.view(-1, nsh[0])
+        Q, _ = D.qr(D.matmul(Z, w))
+        assert Q.shape[1] == rk[i + 1], (Q.shape, rk)
+        out[i] = Q.view(rk[i], *tt[i].shape[1:-1], rk[i + 1])
+        M = D.einsum("ki,kj->ij", Q, Z)
+        cur = D.matmul(M, D.contig(tt[i + 1]).view(nsh[0], -1)).view(rk[i + 1], *nsh[1:])
+    out[d - 1] = cur
+    return out
+
+
+def _randorth_args(tt, gs):
+    d = len(tt)
+    I64 = ctypes.c_int64
+    inner = (I64 * d)(*[_inner(c) for c in tt])
+    ranks = (I64 * (d + 1))(*([tt[0].shape[0]] + [c.shape[-1] for c in tt]))
+    sranks = (I64 * (d + 1))(*([gs[0].shape[0]] + [c.shape[-1] for c in gs]))
+    return inner, ranks, sranks
+
+
+def randorth_lds(tt, gs):
+    """Bytes of LDS `ttk_rand_orth` needs for this train and sketch, -1 if they do not fit one
+    workgroup (the composed path then runs)."""
+    return int(D.lib.ttk_rand_orth_lds(len(tt), *_randorth_args(tt, gs)))
+
+
+def _randorth_native(tt, gs):
+    """`ttk_rand_orth`: the whole sweep in one launch of one workgroup, into one fresh buffer (the
+    output cores are views of it).  No host read: the ranks come from `randorth_ranks`."""
+    d = len(tt)
+    inner, ranks, sranks = _randorth_args(tt, gs)
+    rk = randorth_ranks(ranks[0], inner[:d - 1], sranks[1:d]) + [ranks[d]]
+    cs = [D.contig(c) for c in tt]
+    ss = [D.contig(c) for c in gs]
+    sizes = [rk[k] * inner[k] * rk[k + 1] for k in range(d)]
+    offs = np.concatenate(([0], np.cumsum([(s + 1) & ~1 for s in sizes])))  # 16-byte aligned cores
+    buf = D.empty(int(offs[-1]))
+    outs = [buf[int(offs[k]):int(offs[k]) + sizes[k]] for k in range(d)]
+    P = ctypes.c_void_p
+    got = (ctypes.c_int64 * (d + 1))()
+    D._stream()
+    D.check(D.lib.ttk_rand_orth(D.ctx(), d, (P * d)(*[c.data_ptr() for c in cs]), inner, ranks,
+                                (P * d)(*[c.data_ptr() for c in ss]), sranks,
+                                (P * d)(*[o.data_ptr() for o in outs]), got), "rand_orth")
+    assert list(got) == rk, (list(got), rk)
+    return [o.view(rk[k], *tt[k].shape[1:-1], rk[k + 1]) for k, o in enumerate(outs)]
+
+
+def _use_native_randorth(tt, gs):
+    return (NATIVE_RANDORTH and D.DEV.type == "cuda" and hasattr(D.lib, "ttk_rand_orth")
+            and randorth_lds(tt, gs) >= 0)
+
+
+def _tt_lr_random_orthogonalise(tt, gs):
+    """`src/tt_ops.py:89-101`: with W = tt_rl_contraction(tt, gs), for i = 0..d-2: Z = core i as
+    (r_i n_i, R_{i+1}), Q = economic QR of Z W_{i+1}, core i <- Q, core i+1 <- (Q^T Z) core i+1.  The
+    output ranks are `randorth_ranks` (fixed by the sketch's ranks, no truncation decision), every core
+    but the last has an orthonormal left unfolding.  With the sketch in hand the sweep reads nothing
+    back to the host (the host read of `tt_lr_random_orthogonalise` is `tt_random_gaussian`'s
+    normalisation).  The caller's tensors are never written; the list is rebound in place, like the
+    reference's list mutation.  One launch (`ttk_rand_orth`) when the train fits one workgroup's LDS,
+    else composed from einsum / QR launches (TTIPM_NATIVE_RANDORTH=0: always composed)."""
+    if len(tt) < 2:
+        return tt
+    out = _randorth_native(tt, gs) if _use_native_randorth(tt, gs) else _randorth_composed(tt, gs)
+    tt[:] = out
+    return tt
+
+
+def _tt_rl_random_orthogonalise(tt, gs):
+    """`src/tt_ops.py:83-86`: the mirrored sweep (right unfoldings orthonormal, ranks fixed from the
+    right), through `tt_swap_all`."""
+    if len(tt) < 2:
+        return tt
+    out = tt_swap_all(_tt_lr_random_orthogonalise(tt_swap_all(tt), tt_swap_all(gs)))
+    tt[:] = out
+    return tt
+
+
+def tt_lr_random_orthogonalise(tt, target_ranks):
+    """`src/tt_ops.py:68-72`: rounding to the given bond ranks with a fresh Gaussian sketch
+    (`tt_random_gaussian`: host MT19937 draws and one host read for its normalisation)."""
+    if len(tt) > 1:
+        gs = tt_random_gaussian(target_ranks, shape=tuple(tt[0].shape[1:-1]))
+        return _tt_lr_random_orthogonalise(tt, gs)
+    return tt
+
+
+def tt_rl_random_orthogonalise(tt, target_ranks):
+    """`src/tt_ops.py:75-80`: as above from the right; the sketch is drawn left to right and mirrored."""
+    if len(tt) > 1:
+        gs = tt_swap_all(tt_random_gaussian(target_ranks, shape=tuple(tt[0].shape[1:-1])))
+        out = tt_swap_all(_tt_lr_random_orthogonalise(tt_swap_all(tt), gs))
+        tt[:] = out
+        return tt
+    return tt
+
+
 # ------------------------------------------------------------------ zip-up products (`:391-502`)
 def swap_cores(a, b, eps):
     """`cy_src/tt_ops_cy.pyx:393-426`"""
