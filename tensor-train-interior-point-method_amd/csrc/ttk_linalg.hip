@@ -234,99 +234,6 @@ __global__ __launch_bounds__(256) void svd_big_round_kernel(double *__restrict__
   if (lane == 0) *flag = 1;
 }
 
-// One launch per Jacobi SWEEP instead of per round (TTK_KNOB_SVD_SWEEP_ONE): the P/2 pair waves of
-// svd_big_round_kernel stay resident for all P-1 rounds of the sweep, and a wave starts its pair of
-// round r as soon as its two columns have finished round r-1 -- per-column round counters `colr`
-// (in-launch hand-offs, ttk_common.h: sc1 stores, drain, agent-scope release; the consumer polls, then
-// acquires and loads with sc1), no grid-wide barrier.  Each column belongs to exactly one pair per
-// round, so a column's rounds are totally ordered through its counter, and every rotation is
-// svd_big_round_kernel's: the same expressions on the same values in the same round order
-// (bit-identical, tools/dump_kernels.py).  The wave's pair index is its workgroup's start ticket x 4
-// + its wave index.  A wave waits only for waves of the previous round, which wait only for earlier
-// rounds; round 0 never waits, so with every workgroup resident the launch drains -- the grid is
-// P/8 <= 256 workgroups of 256 threads, far below the chip's resident capacity, and a poll past
-// DEP_SPIN_MAX gives up and is counted (dep[1], ttk_dep_timeouts) instead of hanging.
-// colr[c] = base + (rounds of this sweep column c has finished); the host zeroes colr per SVD and
-// passes base = sweep * (P - 1).
-__device__ __forceinline__ void colr_wait(const unsigned *colr, int a, int b, unsigned target, unsigned *dep) {
-  if ((threadIdx.x & 63) == 0) {
-    const __attribute__((address_space(1))) unsigned *ca = (const __attribute__((address_space(1))) unsigned *)(colr + a);
-    const __attribute__((address_space(1))) unsigned *cb = (const __attribute__((address_space(1))) unsigned *)(colr + b);
-    long n = 0;
-    while ((int)(__hip_atomic_load(ca, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) < 0 ||
-           (int)(__hip_atomic_load(cb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) < 0) {
-      __builtin_amdgcn_s_sleep(1);
-      if (++n > ttk::DEP_SPIN_MAX) {
-        __hip_atomic_fetch_add(dep + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        break;
-      }
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-#ifndef TTK_HANDOFF_RELAXED
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
-  __atomic_signal_fence(__ATOMIC_SEQ_CST);  // no column load moves above the poll
-}
-
-__global__ __launch_bounds__(256) void svd_big_sweep_kernel(double *__restrict__ W, double *__restrict__ V, int p,
-                                                            int q, double tol, int *__restrict__ flag, unsigned *colr,
-                                                            unsigned base, unsigned *dep, unsigned tick_base) {
-  const int P = (p % 2) ? p + 1 : p;
-  const int k = ttk::ticket(dep, tick_base) * 4 + (int)(threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (k >= P / 2) return;  // whole wave exits together (no pair: nobody waits for it)
-  bool rot = false;
-  for (int r = 0; r < P - 1; ++r) {
-    int a, b;
-    rr_pair(P, r, k, a, b);
-    colr_wait(colr, a, b, base + (unsigned)r, dep);
-    if (b < p) {
-      double *wa = W + (int64_t)a * q, *wb = W + (int64_t)b * q;
-      double al = 0.0, be = 0.0, ga = 0.0;
-#pragma unroll 8
-      for (int i = lane; i < q; i += 64) {
-        const double x = ttk::ld_sc1(wa + i), y = ttk::ld_sc1(wb + i);
-        al += x * x;
-        be += y * y;
-        ga += x * y;
-      }
-      al = ttk::wave_sum(al);
-      be = ttk::wave_sum(be);
-      ga = ttk::wave_sum(ga);
-      if (!(al < 1e-300 || be < 1e-300) && !(ga * ga <= tol * tol * al * be)) {
-        double c, s;
-        jacobi_rotation(al, be, ga, c, s);
-#pragma unroll 8
-        for (int i = lane; i < q; i += 64) {
-          const double x = ttk::ld_sc1(wa + i), y = ttk::ld_sc1(wb + i);
-          ttk::st_sc1(wa + i, c * x - s * y);
-          ttk::st_sc1(wb + i, s * x + c * y);
-        }
-        double *va = V + (int64_t)a * p, *vb = V + (int64_t)b * p;
-#pragma unroll 8
-        for (int i = lane; i < p; i += 64) {
-          const double x = ttk::ld_sc1(va + i), y = ttk::ld_sc1(vb + i);
-          ttk::st_sc1(va + i, c * x - s * y);
-          ttk::st_sc1(vb + i, s * x + c * y);
-        }
-        rot = true;
-      }
-    }
-    // publish both columns' round r: drain the sc1 stores, release, then the counters
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifndef TTK_HANDOFF_RELAXED
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-    if (lane == 0) {
-      __hip_atomic_store(colr + a, base + (unsigned)r + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(colr + b, base + (unsigned)r + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  if (rot && lane == 0) *flag = 1;
-}
-
 __global__ __launch_bounds__(1024) void svd_big_finish_kernel(double *W, double *V, double *sig, int *rank, int m,
                                                               int n, double *__restrict__ U, double *__restrict__ S,
                                                               double *__restrict__ Vt) {
@@ -1782,7 +1689,7 @@ __device__ __forceinline__ void syev_rank2_rows_b(double *__restrict__ A22, int 
 template <int NT, int GG = NT / 128>
 __global__ __launch_bounds__(NT) void syev_small_kernel(const double *__restrict__ Ain, int n, int which,
                                                         double *__restrict__ ev_out, double *__restrict__ vec_out,
-                                                        int timing, int var) {
+                                                        int timing) {
   constexpr int NW = NT / 64, G = GG;  // waves; lanes per row in the symv
   extern __shared__ double lds[];
   const int ld = n | 1;
@@ -1798,11 +1705,11 @@ __global__ __launch_bounds__(NT) void syev_small_kernel(const double *__restrict
   __syncthreads();
   // two barriers per reflector: wave 0 owns A22's first row in the rank-2 update, so right after
   // updating it (same wave, LDS order) it builds the next reflector from that row while the other
-  // waves finish their rows; nobody else reads the row in that phase.  `var` (TTK_SYEV_VAR, A/B
-  // timing; every setting bit-identical): 4 = the symv's lane-group sums by DPP instead of LDS
-  // permutes, 8 (4 waves) / 16 (16 waves) = wave 0 updates row 0 only (it was the last to reach the
-  // step's second barrier: its share of the rows plus the reflector), the other waves the remaining
-  // rows -- n = 40 134.7 -> 126.2 us with 4 waves, slower with 16 (r05_syev_small.txt).
+  // waves finish their rows; nobody else reads the row in that phase.  The symv's lane-group sums
+  // go by DPP, not LDS permutes.  With 4 or 8 waves, wave 0 updates row 0 only (it was the last to
+  // reach the step's second barrier: its share of the rows plus the reflector) and the other waves
+  // the remaining rows -- n = 40 134.7 -> 126.2 us with 4 waves; with 16 waves the split is slower,
+  // so there every wave takes its share (r05_syev_small.txt).
   auto reflector = [&](int k) {  // wave 0: dlarfg on row k (the sub-column by symmetry)
     double *v = A + k * ld + k + 1;
     const int m = n - k - 1;
@@ -1858,12 +1765,7 @@ __global__ __launch_bounds__(NT) void syev_small_kernel(const double *__restrict
           for (; j < m; j += G) acc = fma(ar[j], v[j], acc);
           acc = (acc + a1) + (a2 + a3);
         }
-        if (var & 4) {  // DPP: the xor-butterfly's sums (both lanes of a pair hold a + b), no LDS permutes
-          acc = ttk::group_sum<G>(acc);
-        } else {
-#pragma unroll
-          for (int o = 1; o < G; o <<= 1) acc += __shfl_xor(acc, o, 64);
-        }
+        acc = ttk::group_sum<G>(acc);  // DPP: the xor-butterfly's sums (both lanes of a pair hold a + b)
         if (h == 0 && r < m) pv[r] = tau * acc;
       }
       TTK_SSTAMP(0)
@@ -1875,7 +1777,7 @@ __global__ __launch_bounds__(NT) void syev_small_kernel(const double *__restrict
       const double K = 0.5 * tau * ttk::wave_sum(fma(p0, v0, p1 * v1));
       const double w0 = fma(-K, v0, p0), w1 = fma(-K, v1, p1);
       TTK_SSTAMP(2)
-      if (var & (NT <= 512 ? 8 : 16)) {  // wave 0 updates row 0 only, then the next reflector
+      if constexpr (NT <= 512) {  // wave 0 updates row 0 only, then the next reflector
         if (wid == 0)
           syev_rank2_rows_b<1>(A + (k + 1) * ld + k + 1, ld, v, pv, m, 0, m, K, j0, j1, v0, v1, w0, w1, fpiv + n);
         else
@@ -3130,30 +3032,10 @@ static int svd_big(void *stream, const double *A, int m, int n, double *U, doubl
   const double tol = EPS * (p > 16 ? (double)p : 16.0);
   const int P = (kk % 2) ? kk + 1 : kk;
   const int grid = (P / 2 * 64 + 255) / 256;
-  ttk::Ctx &cx = ttk::ctx();
-  const bool one = cx.knob[TTK_KNOB_SVD_SWEEP_ONE] != 0 && kk > 1;
-  if (one) {  // per-column round counters (zeroed per SVD) and the context's hand-off words
-    if (cx.colr_n < P) {
-      if (cx.colr) (void)hipFree(cx.colr);
-      cx.colr = nullptr;
-      cx.colr_n = 0;
-      TTK_HIP(hipMalloc(reinterpret_cast<void **>(&cx.colr), sizeof(unsigned) * (size_t)P));
-      cx.colr_n = P;
-    }
-    TTK_HIP(hipMemsetAsync(cx.colr, 0, sizeof(unsigned) * (size_t)P, st));
-    rc = ttk::dep_counter(stream);
-    if (rc != TTK_OK) return rc;
-  }
   for (int sweep = 0; sweep < 60 && kk > 1; ++sweep) {
     TTK_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
-    if (one) {
-      hipLaunchKernelGGL(svd_big_sweep_kernel, dim3(grid), dim3(256), 0, st, X, V, kk, p, tol, flag, cx.colr,
-                         (unsigned)sweep * (unsigned)(P - 1), cx.dep, cx.tick_total);
-      cx.tick_total += (unsigned)grid;
-    } else {
-      for (int r = 0; r < P - 1; ++r)
-        hipLaunchKernelGGL(svd_big_round_kernel, dim3(grid), dim3(256), 0, st, X, V, kk, p, r, tol, flag);
-    }
+    for (int r = 0; r < P - 1; ++r)
+      hipLaunchKernelGGL(svd_big_round_kernel, dim3(grid), dim3(256), 0, st, X, V, kk, p, r, tol, flag);
     TTK_LAUNCH_CHECK();
     int h = 0;
     TTK_HIP(hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -3537,7 +3419,6 @@ int64_t ttk_syev_extreme_work(int n) {
 }
 
 static int g_syev_fused_max = TRI_FUSED_MAX;
-static int g_syev_var = getenv("TTK_SYEV_VAR") ? atoi(getenv("TTK_SYEV_VAR")) : 12;  // syev_small_kernel variants
 static int g_syev_small_wide = getenv("TTK_SYEV_WIDE") ? atoi(getenv("TTK_SYEV_WIDE")) : 64;  // 16-wave small kernel from this n
 static int g_tri_rows = getenv("TTK_TRI_ROWS") ? atoi(getenv("TTK_TRI_ROWS")) : 4;  // largest n for the one-launch-per-step tridiagonalisation
 
@@ -3629,16 +3510,14 @@ int ttk_syev_extreme(void *stream, const double *A, int n, int which, double *ev
     const size_t shm_s = (size_t)syev_small_need(n) * sizeof(double);
     if (n >= g_syev_small_wide) {
       allow_big_lds(syev_small_kernel<1024>, shm_s);
-      hipLaunchKernelGGL(syev_small_kernel<1024>, dim3(1), dim3(1024), shm_s, st, A, n, which, ev, vec, g_svd_timing,
-                         g_syev_var);
+      hipLaunchKernelGGL(syev_small_kernel<1024>, dim3(1), dim3(1024), shm_s, st, A, n, which, ev, vec, g_svd_timing);
     } else if (ttk::ctx().knob[TTK_KNOB_SYEV_WAVES8]) {
       allow_big_lds(syev_small_kernel<512, 2>, shm_s);
       hipLaunchKernelGGL((syev_small_kernel<512, 2>), dim3(1), dim3(512), shm_s, st, A, n, which, ev, vec,
-                         g_svd_timing, g_syev_var);
+                         g_svd_timing);
     } else {
       allow_big_lds(syev_small_kernel<256>, shm_s);
-      hipLaunchKernelGGL(syev_small_kernel<256>, dim3(1), dim3(256), shm_s, st, A, n, which, ev, vec, g_svd_timing,
-                         g_syev_var);
+      hipLaunchKernelGGL(syev_small_kernel<256>, dim3(1), dim3(256), shm_s, st, A, n, which, ev, vec, g_svd_timing);
     }
     TTK_LAUNCH_CHECK();
     return TTK_OK;

@@ -388,9 +388,13 @@ def _sym_cases(n, rng):
     yield "scaled", 1e-6 * (M + M.T) + np.diag(np.arange(n, dtype=float))
 
 
-@pytest.mark.parametrize("n", [1, 2, 3, 4, 10, 64, 100, 127, 128, 129, 139, 140, 288, 600, 800])
+@pytest.mark.parametrize("n", [1, 2, 3, 4, 10, 64, 100, 127, 128, 129, 139, 140, 150, 256, 257, 258, 288, 300, 512, 513,
+                               600, 800])
 @pytest.mark.parametrize("largest", [False, True])
 def test_syev_extreme(dev, n, largest):
+    """sizes on every boundary of the default path: the LDS kernels up to 128, the hoisted per-step
+    tridiagonalisation <1,1,4> up to 256 and <2,2,8> for 257..512, tri_step_kernel from 513, the staged
+    back-transform up to 513, the two-launch multi-workgroup form beyond"""
     rng = _rng(7 * n + largest)
     for name, A in _sym_cases(n, rng):
         lam, v = dev.syev_extreme(dev.from_numpy(A), largest=largest)
@@ -543,11 +547,9 @@ def test_syev_tri_persistent_launch_bit_identical(dev, n):
 
 @pytest.mark.parametrize("m,n,graded", [(150, 120, 0), (120, 150, 1), (300, 200, 1), (97, 97, 0), (400, 130, 0),
                                         (260, 255, 1)])
-def test_svd_sweep_one_launch_bit_identical(dev, m, n, graded):
-    """the multi-workgroup Jacobi SVD (min(m,n) > 96) with one launch per sweep (TTK_KNOB_SVD_SWEEP_ONE:
-    resident pair waves, per-column round hand-offs) and with one launch per round give the same U, S,
-    Vt bit for bit, and the factorisation holds; no hand-off wait timed out"""
-    from ttipm_amd import _lib
+def test_svd_multi_workgroup_factorisation(dev, m, n, graded):
+    """the multi-workgroup Jacobi SVD (min(m,n) > 96, one launch per round-robin round) factorises A,
+    full-rank and graded to 1e-15; no hand-off wait timed out"""
     rng = _rng(7 * m + n)
     k = min(m, n)
     A = rng.standard_normal((m, n))
@@ -555,17 +557,8 @@ def test_svd_sweep_one_launch_bit_identical(dev, m, n, graded):
         Uq, _ = np.linalg.qr(rng.standard_normal((m, k)))
         Vq, _ = np.linalg.qr(rng.standard_normal((n, k)))
         A = (Uq * np.logspace(0, -15, k)) @ Vq.T
-    out = []
-    for v in (1, 0):
-        old = _set_knob(_lib.KNOB_SVD_SWEEP_ONE, v)
-        try:
-            U, S, Vt, s = dev.svd(dev.from_numpy(A))
-        finally:
-            _set_knob(_lib.KNOB_SVD_SWEEP_ONE, old)
-        out.append((dev.read(U), dev.read(S), dev.read(Vt)))
-    for a, b in zip(*out):
-        assert np.array_equal(a, b)
-    U, S, Vt = out[0]
+    U, S, Vt, s = dev.svd(dev.from_numpy(A))
+    U, S, Vt = dev.read(U), dev.read(S), dev.read(Vt)
     assert np.abs((U * S) @ Vt - A).max() <= 1e-12 * max(1.0, np.abs(A).max()) * np.sqrt(k)
     dev.check_handoffs()
 

@@ -36,7 +36,7 @@ def step_phases():
 
 
 def totals():
-    """Default-path latency per n (no timers), for A/B across TTK_SYEV_VAR settings."""
+    """Default-path latency per n (no timers), for A/B across library builds."""
     rng = np.random.default_rng(0)
     st = D._stream()
     out = []

@@ -1,6 +1,5 @@
-"""Per-call wall time of the one-launch forms against the per-step launches they replace (same
-arithmetic): the multi-workgroup Jacobi SVD with one launch per sweep (TTK_KNOB_SVD_SWEEP_ONE) or per
-round, and the multi-workgroup tridiagonalisation of the extreme eigenpair with every step in one
+"""Per-call wall time of the one-launch form against the per-step launches it replaces (same
+arithmetic): the multi-workgroup tridiagonalisation of the extreme eigenpair with every step in one
 launch (TTK_KNOB_TRI_PERSIST) or one launch per step.  Alternating off / on / off / on.
     python tools/bench_persist.py"""
 import os
@@ -32,10 +31,6 @@ def timed(knob, fn, reps=5):
     return row
 
 
-for (m, n) in [(120, 100), (150, 120), (200, 130), (260, 255), (400, 130), (600, 400)]:
-    A = D.from_numpy(rng.standard_normal((m, n)))
-    row = timed(_lib.KNOB_SVD_SWEEP_ONE, lambda: D.svd(A))
-    print(f"svd {m}x{n}: per round {row[0]:.3f} / {row[2]:.3f} ms, per sweep {row[1]:.3f} / {row[3]:.3f} ms", flush=True)
 for n in (129, 144, 192, 256, 300, 352, 512):
     M = rng.standard_normal((n, n))
     A = D.from_numpy(M + M.T)
