@@ -531,6 +531,36 @@ int ttk_rand_orth(ttk_ctx ctx, int d, const double *const *cores, const int64_t 
                   const double *const *sketch, const int64_t *sketch_ranks, double *const *out,
                   int64_t *out_ranks);
 
+/* Generalised Nystroem TT rounding in three launches (`_tt_generalised_nystroem`, src/tt_ops.py:
+ * 273-292, with the sketch contractions of `tt_lr_contraction` / `tt_rl_contraction`, src/tt_ops.py:
+ * 51-65).  For the train A, a left sketch G (bond ranks lranks; `tt_gaussian_1`) and a right sketch B
+ * (bond ranks rranks; `tt_gaussian_2`), per interior bond k = 1 .. d-1: W_L[k] (lranks[k] x ranks[k])
+ * is the left-to-right partial contraction of G and A, W_R[k] (ranks[k] x rranks[k]) the right-to-
+ * left one of A and B, P = W_L[k] W_R[k] = U diag(S) V^T (thin), L_k = W_R V diag(1/sqrt(S)),
+ * R_k = diag(1/sqrt(S)) U^T W_L, and out_k = R_k core_k L_{k+1} on the unfoldings (no R on core 0, no
+ * L on core d-1).  Launch 1 (2 workgroups) runs the two sketch chains, launch 2 (d-1 workgroups)
+ * one one-sided Jacobi SVD per bond in LDS (fixed pair order, at most 30 sweeps, S sorted
+ * descending), launch 3 (d workgroups) the core updates; W_L, W_R, L and R live in one stream-ordered
+ * scratch block and stream order is the only dependency.  No truncation decision and no host read:
+ * out_ranks[0] = ranks[0], out_ranks[d] = ranks[d], out_ranks[k] = min(lranks[k], rranks[k]), and
+ * the call returns after enqueueing.  Like the reference, nothing guards a zero singular value.
+ * Fixed summation and rotation order: two calls on the same input give the same bits.
+ * cores[k]: device, contiguous (ranks[k], inner[k], ranks[k+1]) fp64, read only; sk_left[k] and
+ * sk_right[k] likewise with lranks and rranks (sk_left[d-1] and sk_right[0] are never read; the
+ * boundary ranks agree: ranks[0] == lranks[0] == rranks[0], and likewise at d); out[k]: caller-owned
+ * contiguous buffers of out_ranks[k] inner[k] out_ranks[k+1] doubles that overlap no input; ranks,
+ * lranks, rranks, out_ranks: d+1 entries.  ttk_nystroem_lds: the largest dynamic-LDS request of the
+ * three launches in bytes, or -1 when some core does not fit one workgroup (at most 160 KiB and 32
+ * cores) or the arguments are invalid -- the caller then composes the rounding from ttk_einsum and
+ * ttk_svd.  ttk_nystroem validates on the host (d >= 2, every rank and extent >= 1, equal boundary
+ * ranks, no null pointer it needs, the LDS fit) and returns TTK_ERR_ARG without launching when a
+ * check fails. */
+int64_t ttk_nystroem_lds(int d, const int64_t *inner, const int64_t *ranks, const int64_t *lranks,
+                         const int64_t *rranks);
+int ttk_nystroem(ttk_ctx ctx, int d, const double *const *cores, const int64_t *inner, const int64_t *ranks,
+                 const double *const *sk_left, const int64_t *lranks, const double *const *sk_right,
+                 const int64_t *rranks, double *const *out, int64_t *out_ranks);
+
 /* Dense Schur-complement local KKT solve in one call (SURVEY §8(b) `ttk_local_assemble` +
  * `ttk_dense_schur_solve`; the dense branch of `_ipm_local_solver`, src/tt_ipm.py:183-229):
  * assembles L_XI = B22 diag(inv_I), L_eq = B01, L_Z = B21 (each 'lsr,smnS,LSR->lmLrnR'), Cholesky of

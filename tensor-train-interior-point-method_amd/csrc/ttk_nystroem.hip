@@ -1,0 +1,418 @@
+// Generalised Nystroem TT rounding in THREE launches of independent workgroups (`ttk_nystroem`):
+// `_tt_generalised_nystroem` (src/tt_ops.py:273-292) with the sketch contractions of
+// `tt_lr_contraction` / `tt_rl_contraction` (src/tt_ops.py:51-65).
+//
+//   launch 1, grid 2     workgroup 0 walks right to left, W_R[k] = unfold(A_k W_R[k+1]) unfold(B_k)^T
+//                        (A the train, B the right sketch: ttk_rand_orth's phase A); workgroup 1 walks
+//                        left to right, W_L[k+1] = unfold(G_k)^T unfold(W_L[k] A_k) (G the left sketch),
+//                        directly on the cores as they lie (no mirrored copies);
+//   launch 2, grid d-1   workgroup k-1 forms P = W_L[k] W_R[k] in LDS, runs a one-sided Jacobi SVD on
+//                        it and writes L_k = W_R V diag(1/sqrt(S)) and R_k = diag(1/sqrt(S)) U^T W_L;
+//   launch 3, grid d     workgroup k writes out_k = R_k core_k L_{k+1} (no R on core 0, no L on the last).
+//
+// W_L, W_R, L and R live in one stream-ordered scratch block per call; stream order is the only
+// dependency between the launches.  No truncation decision and no host read: the output ranks are
+// min(lranks[k], rranks[k]), host arithmetic.  Inside a launch no workgroup waits on another:
+// workgroup barriers only, no spin wait, no atomics, every loop bounded (the Jacobi sweeps by
+// NY_SWEEPS), so nothing depends on co-residency.  Every product sums k ascending in one fma chain
+// per output element and every reduction is a fixed wave tree; the Jacobi pairs follow one fixed
+// round-robin order.  Two calls on the same input therefore give the same bits.
+//
+// The Jacobi rotates the rows of P when lranks[k] <= rranks[k] and the rows of P^T otherwise, so it
+// always works on p = min(l, s) rows of length max(l, s): G P = diag(S) V^T with G = U^T the
+// accumulated rotations (or G P^T = diag(S) U^T with G = V^T).  One wave takes one pair; the p/2
+// disjoint pairs of a round run in parallel, one barrier per round.  Singular values are sorted
+// descending (ties by row index).  Like the reference, nothing guards a zero singular value.
+//
+// The products are VALU fma chains: at the extents this call accepts (each core with its factors in
+// 160 KiB of LDS, bond ranks of a few tens at most) a 16x16x4 fp64 MFMA tile would be mostly
+// padding, and the three launches are bound by their latency, not by their FLOPs.
+#include <hip/hip_runtime.h>
+
+#include "ttk_common.h"
+#include "ttk_internal.h"
+#include "ttk_tt_gemm.h"
+
+namespace {
+
+constexpr int NY_MAXD = 32;                  // cores per train (the plan travels as a kernel argument)
+constexpr int64_t NY_LDS_MAX = 160 * 1024;   // bytes one workgroup may declare
+constexpr int NY_SWEEPS = 30;                // hard cap of the Jacobi sweeps (they converge in under 10)
+constexpr int NY_FLAGS = 16;                 // doubles that hold the NY_SWEEPS per-sweep rotation flags
+constexpr double NY_EPS = 2.220446049250313e-16;
+
+struct NyPlan {
+  int d, nt1;
+  int n[NY_MAXD];       // middle extents
+  int r[NY_MAXD + 1];   // train bond ranks
+  int l[NY_MAXD + 1];   // left sketch bond ranks
+  int s[NY_MAXD + 1];   // right sketch bond ranks
+  int q[NY_MAXD + 1];   // output bond ranks
+  int owl[NY_MAXD], owr[NY_MAXD], ofl[NY_MAXD], ofr[NY_MAXD];  // W_L, W_R, L, R of bond k in the scratch block
+  int oC, oZ, oY, oW;   // launch 1's LDS regions (offsets in doubles, all even: 16-byte aligned)
+  const double *core[NY_MAXD];
+  const double *skl[NY_MAXD];
+  const double *skr[NY_MAXD];
+  double *out[NY_MAXD];
+};
+
+__host__ __device__ inline int64_t ny_even(int64_t v) { return (v + 1) & ~(int64_t)1; }
+
+// doubles of LDS launch 2 needs for a bond with W_L (l x r) and W_R (r x s)
+__host__ __device__ inline int64_t ny_bond_words(int64_t l, int64_t r, int64_t s) {
+  const int64_t p = l < s ? l : s;
+  return ny_even(l * r) + ny_even(r * s) + ny_even(l * s) + ny_even(p * p) + 2 * ny_even(p) + NY_FLAGS;
+}
+
+// doubles of LDS launch 3 needs for a core (r, n, r1) with R (q x r) and L (r1 x q1); q = 0 / q1 = 0:
+// the first / last core, which has no such factor
+__host__ __device__ inline int64_t ny_core_words(int64_t q, int64_t r, int64_t n, int64_t r1, int64_t q1) {
+  return ny_even(r * n * r1) + ny_even(q * r) + ny_even(r1 * q1) + ny_even(r * n * q1);
+}
+
+// Validates the extents and lays out scratch and LDS.  Returns the largest dynamic-LDS request of the
+// three launches in bytes, -1 when some core does not fit one workgroup (or the train has more than
+// NY_MAXD cores), -2 on invalid arguments.  shm[3]: bytes per launch; *words: doubles of scratch.
+int64_t ny_plan(int d, const int64_t *inner, const int64_t *ranks, const int64_t *lranks, const int64_t *rranks,
+                NyPlan *p, int64_t *shm, int64_t *words) {
+  if (d < 2 || !inner || !ranks || !lranks || !rranks) return -2;
+  for (int k = 0; k <= d; ++k)
+    if (ranks[k] < 1 || lranks[k] < 1 || rranks[k] < 1) return -2;
+  for (int k = 0; k < d; ++k)
+    if (inner[k] < 1) return -2;
+  if (ranks[0] != lranks[0] || ranks[0] != rranks[0] || ranks[d] != lranks[d] || ranks[d] != rranks[d]) return -2;
+  if (d > NY_MAXD) return -1;
+  const int64_t cap = NY_LDS_MAX / 8;  // no single extent or product may pass the LDS capacity
+  for (int k = 0; k <= d; ++k)
+    if (ranks[k] > cap || lranks[k] > cap || rranks[k] > cap) return -1;
+  for (int k = 0; k < d; ++k)
+    if (inner[k] > cap) return -1;
+  const int64_t *n = inner, *r = ranks, *l = lranks, *s = rranks;
+  bool over = false;
+  auto p3 = [&](int64_t a, int64_t b, int64_t c) {  // a b c, saturating at cap + 1 (factors <= cap: no overflow)
+    int64_t v = a * b;
+    v = v > cap ? cap + 1 : v * c;
+    if (v > cap) over = true, v = cap + 1;
+    return v;
+  };
+  // launch 1: the core, the sketch core, the intermediate and the running W of either chain
+  int64_t zC = 2, zZ = 2, zY = 2, zW = 2;
+  auto up = [](int64_t &z, int64_t v) { z = v > z ? v : z; };
+  for (int k = 0; k < d; ++k) up(zC, p3(r[k], n[k], r[k + 1]));
+  for (int k = 1; k < d; ++k) up(zZ, p3(s[k], n[k], s[k + 1]));
+  for (int k = 0; k + 1 < d; ++k) up(zZ, p3(l[k], n[k], l[k + 1]));
+  for (int k = 1; k + 1 < d; ++k) {
+    up(zY, p3(r[k], n[k], s[k + 1]));
+    up(zY, p3(l[k], n[k], r[k + 1]));
+  }
+  if (over) return -1;
+  int64_t w = 0, b2 = 0, b3 = 0;
+  for (int k = 1; k < d; ++k) {
+    const int64_t lr = p3(l[k], r[k], 1), rs = p3(r[k], s[k], 1), ls = p3(l[k], s[k], 1);
+    up(zW, lr);
+    up(zW, rs);
+    if (over) return -1;
+    if (p) {
+      p->owl[k] = (int)w, p->owr[k] = (int)(w + ny_even(lr));
+      p->ofl[k] = (int)(w + ny_even(lr) + ny_even(rs)), p->ofr[k] = (int)(w + ny_even(lr) + 2 * ny_even(rs));
+    }
+    w += ny_even(lr) + 2 * ny_even(rs) + ny_even(lr);  // W_L, W_R, L (r x q <= r x s), R (q x r <= l x r)
+    if (w > ((int64_t)1 << 30)) return -1;
+    up(b2, ny_bond_words(l[k], r[k], s[k]));
+  }
+  for (int k = 0; k < d; ++k) {
+    const int64_t q = k > 0 ? (l[k] < s[k] ? l[k] : s[k]) : 0;
+    const int64_t q1 = k + 1 < d ? (l[k + 1] < s[k + 1] ? l[k + 1] : s[k + 1]) : 0;
+    p3(r[k], n[k], q1 > 0 ? q1 : 1);
+    if (over) return -1;
+    up(b3, ny_core_words(q, r[k], n[k], r[k + 1], q1));
+  }
+  if (over) return -1;
+  const int64_t b1 = ny_even(zC) + ny_even(zZ) + ny_even(zY) + ny_even(zW);
+  int64_t big = b1 > b2 ? b1 : b2;
+  big = big > b3 ? big : b3;
+  if (big * 8 > NY_LDS_MAX) return -1;
+  if (shm) shm[0] = b1 * 8, shm[1] = b2 * 8, shm[2] = b3 * 8;
+  if (words) *words = w;
+  if (p) {
+    p->d = d;
+    for (int k = 0; k < d; ++k) p->n[k] = (int)n[k];
+    for (int k = 0; k <= d; ++k) {
+      p->r[k] = (int)r[k];
+      p->l[k] = (int)l[k];
+      p->s[k] = (int)s[k];
+      p->q[k] = (int)(k == 0 || k == d ? r[k] : (l[k] < s[k] ? l[k] : s[k]));
+    }
+    int64_t o = 0;
+    p->oC = (int)o, o += ny_even(zC);
+    p->oZ = (int)o, o += ny_even(zZ);
+    p->oY = (int)o, o += ny_even(zY);
+    p->oW = (int)o;
+    p->nt1 = (zY > zC ? zY : zC) <= 2048 ? 256 : 1024;  // small trains: fewer waves at each barrier
+  }
+  return big * 8;
+}
+
+// ---- launch 1: the two sketch chains, one workgroup each
+__global__ __launch_bounds__(1024) void nystroem_sketch_kernel(const NyPlan p, double *scr) {
+  extern __shared__ __attribute__((aligned(16))) double ny_lds[];
+  double *C = ny_lds + p.oC, *Z = ny_lds + p.oZ, *Y = ny_lds + p.oY, *W = ny_lds + p.oW;
+  const int d = p.d;
+  if (blockIdx.x == 0) {
+    // right to left: W_R[k] (r_k x s_k) = unfold(A_k W_R[k+1]) (r_k x n s_{k+1}) unfold(B_k)^T
+    for (int k = d - 1; k >= 1; --k) {
+      const int rk = p.r[k], n = p.n[k], r1 = p.r[k + 1], sk = p.s[k], s1 = p.s[k + 1];
+      ro_load(C, p.core[k], rk * n * r1);
+      ro_load(Z, p.skr[k], sk * n * s1);
+      __syncthreads();
+      const double *T = C;  // the last core meets its sketch core directly (r_d == s_d)
+      if (k < d - 1) {
+        ro_gemm(rk * n, s1, r1, [&](int i, int c) { return C[i * r1 + c]; }, [&](int c, int j) { return W[c * s1 + j]; },
+                [&](int i, int j, double v) { Y[i * s1 + j] = v; });
+        __syncthreads();
+        T = Y;
+      }
+      const int K = n * s1;
+      double *wk = scr + p.owr[k];
+      ro_gemm(rk, sk, K, [&](int i, int c) { return T[i * K + c]; }, [&](int c, int j) { return Z[j * K + c]; },
+              [&](int i, int j, double v) {
+                W[i * sk + j] = v;
+                wk[i * sk + j] = v;
+              });
+      __syncthreads();
+    }
+  } else {
+    // left to right: W_L[k+1] (l_{k+1} x r_{k+1}) = unfold(G_k)^T (l_{k+1} x l_k n) unfold(W_L[k] A_k)
+    for (int k = 0; k + 1 < d; ++k) {
+      const int rk = p.r[k], n = p.n[k], r1 = p.r[k + 1], lk = p.l[k], l1 = p.l[k + 1];
+      ro_load(C, p.core[k], rk * n * r1);
+      ro_load(Z, p.skl[k], lk * n * l1);
+      __syncthreads();
+      const double *T = C;  // the first core meets its sketch core directly (r_0 == l_0)
+      const int N = n * r1;
+      if (k > 0) {
+        ro_gemm(lk, N, rk, [&](int i, int c) { return W[i * rk + c]; }, [&](int c, int j) { return C[c * N + j]; },
+                [&](int i, int j, double v) { Y[i * N + j] = v; });
+        __syncthreads();
+        T = Y;
+      }
+      const int K = lk * n;
+      double *wk = scr + p.owl[k + 1];
+      ro_gemm(l1, r1, K, [&](int i, int c) { return Z[c * l1 + i]; }, [&](int c, int j) { return T[c * r1 + j]; },
+              [&](int i, int j, double v) {
+                W[i * r1 + j] = v;
+                wk[i * r1 + j] = v;
+              });
+      __syncthreads();
+    }
+  }
+}
+
+// One sweep-round of the one-sided Jacobi on the rows of A (p x n) with the rotations accumulated in
+// G (p x p): the round's disjoint pairs (circle method over m = p rounded up to even players, the
+// last one fixed) go to the waves in turn.  A pair (i, j) is rotated when |<a_i, a_j>| exceeds
+// tol ||a_i|| ||a_j||.  Returns after a workgroup barrier.
+__device__ void ny_jacobi_round(double *A, double *G, int p, int n, int m, int round, double tol2, int *flag) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  for (int t = wid; t < m / 2; t += nw) {
+    int i = t == 0 ? m - 1 : (round + t) % (m - 1);
+    int j = (round - t + (m - 1)) % (m - 1);
+    if (i > j) {
+      const int x = i;
+      i = j, j = x;
+    }
+    if (j >= p) continue;  // the bye of an odd p
+    double *ai = A + i * n, *aj = A + j * n;
+    double pa = 0.0, pb = 0.0, pg = 0.0;
+    for (int c = lane; c < n; c += 64) {
+      const double x = ai[c], y = aj[c];
+      pa = fma(x, x, pa);
+      pb = fma(y, y, pb);
+      pg = fma(x, y, pg);
+    }
+    const double al = ttk::wave_sum(pa), be = ttk::wave_sum(pb), ga = ttk::wave_sum(pg);
+    if (!(ga * ga > tol2 * al * be)) continue;  // |ga| <= tol sqrt(al be): orthogonal already
+    const double zeta = (be - al) / (2.0 * ga);
+    const double tn = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+    const double cs = 1.0 / sqrt(1.0 + tn * tn), sn = cs * tn;
+    for (int c = lane; c < n; c += 64) {
+      const double x = ai[c], y = aj[c];
+      ai[c] = cs * x - sn * y;
+      aj[c] = sn * x + cs * y;
+    }
+    double *gi = G + i * p, *gj = G + j * p;
+    for (int c = lane; c < p; c += 64) {
+      const double x = gi[c], y = gj[c];
+      gi[c] = cs * x - sn * y;
+      gj[c] = sn * x + cs * y;
+    }
+    if (lane == 0) *flag = 1;
+  }
+  __syncthreads();
+}
+
+// ---- launch 2: workgroup b owns bond k = b + 1
+__global__ __launch_bounds__(1024) void nystroem_bond_kernel(const NyPlan pl, double *scr) {
+  extern __shared__ __attribute__((aligned(16))) double ny_lds[];
+  const int k = blockIdx.x + 1;
+  const int l = pl.l[k], r = pl.r[k], s = pl.s[k];
+  const bool rows = l <= s;  // rotate the rows of P, else those of P^T
+  const int p = rows ? l : s, n = rows ? s : l;
+  double *WL = ny_lds, *WR = WL + ny_even(l * r), *A = WR + ny_even(r * s), *G = A + ny_even(l * s);
+  double *sv = G + ny_even(p * p);
+  int *perm = reinterpret_cast<int *>(sv + ny_even(p));
+  int *flag = reinterpret_cast<int *>(sv + 2 * ny_even(p));
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  ro_load(WL, scr + pl.owl[k], l * r);
+  ro_load(WR, scr + pl.owr[k], r * s);
+  for (int e = threadIdx.x; e < p * p; e += blockDim.x) G[e] = (e / p == e % p) ? 1.0 : 0.0;
+  for (int e = threadIdx.x; e < NY_SWEEPS; e += blockDim.x) flag[e] = 0;
+  for (int e = threadIdx.x; e < p; e += blockDim.x) perm[e] = e;  // stays a valid index whatever the sort meets
+  __syncthreads();
+  // A = P (l x s) or P^T (s x l), P = W_L W_R
+  ro_gemm(l, s, r, [&](int i, int c) { return WL[i * r + c]; }, [&](int c, int j) { return WR[c * s + j]; },
+          [&](int i, int j, double v) { A[rows ? i * s + j : j * l + i] = v; });
+  __syncthreads();
+  const double tol = NY_EPS * (n > 16 ? (double)n : 16.0), tol2 = tol * tol;
+  const int m = (p + 1) & ~1;
+  for (int sweep = 0; sweep < NY_SWEEPS && p > 1; ++sweep) {
+    for (int round = 0; round < m - 1; ++round) ny_jacobi_round(A, G, p, n, m, round, tol2, flag + sweep);
+    if (flag[sweep] == 0) break;  // written before the round's barrier: every thread reads the same value
+  }
+  // sigma_j = ||row j||, sorted descending (ties by index): perm[position] = row
+  for (int j = wid; j < p; j += nw) {
+    double part = 0.0;
+    for (int c = lane; c < n; c += 64) part = fma(A[j * n + c], A[j * n + c], part);
+    const double nrm = sqrt(ttk::wave_sum(part));
+    if (lane == 0) sv[j] = nrm;
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < p; j += blockDim.x) {
+    int pos = 0;
+    for (int i = 0; i < p; ++i) pos += (sv[i] > sv[j] || (sv[i] == sv[j] && i < j)) ? 1 : 0;
+    perm[pos < p ? pos : p - 1] = j;  // a NaN compares false everywhere: stay in bounds
+  }
+  __syncthreads();
+  // rows: G = U^T, A = diag(S) V^T:   R = diag(S^-1/2) G W_L,    L = W_R A^T diag(S^-3/2)
+  // else: G = V^T, A = diag(S) U^T:   L = W_R G^T diag(S^-1/2),  R = diag(S^-3/2) A W_L
+  double *Lk = scr + pl.ofl[k], *Rk = scr + pl.ofr[k];
+  const double *FR = rows ? G : A, *FL = rows ? A : G;  // R's factor has rows of length l, L's of length s
+  ro_gemm(p, r, l, [&](int t, int c) { return FR[perm[t] * l + c]; }, [&](int c, int j) { return WL[c * r + j]; },
+          [&](int t, int j, double v) {
+            const double sg = sv[perm[t]], rt = sqrt(sg);
+            Rk[t * r + j] = rows ? v * (1.0 / rt) : v / (sg * rt);
+          });
+  ro_gemm(r, p, s, [&](int i, int c) { return WR[i * s + c]; }, [&](int c, int t) { return FL[perm[t] * s + c]; },
+          [&](int i, int t, double v) {
+            const double sg = sv[perm[t]], rt = sqrt(sg);
+            Lk[i * p + t] = rows ? v / (sg * rt) : v * (1.0 / rt);
+          });
+}
+
+// ---- launch 3: workgroup k writes out_k = R_k core_k L_{k+1}
+__global__ __launch_bounds__(1024) void nystroem_core_kernel(const NyPlan pl, const double *scr) {
+  extern __shared__ __attribute__((aligned(16))) double ny_lds[];
+  const int k = blockIdx.x, d = pl.d;
+  const int r = pl.r[k], n = pl.n[k], r1 = pl.r[k + 1];
+  const int q = k > 0 ? pl.q[k] : 0, q1 = k + 1 < d ? pl.q[k + 1] : 0;
+  double *C = ny_lds, *R = C + ny_even(r * n * r1), *L = R + ny_even(q * r), *T = L + ny_even(r1 * q1);
+  ro_load(C, pl.core[k], r * n * r1);
+  if (q) ro_load(R, scr + pl.ofr[k], q * r);
+  if (q1) ro_load(L, scr + pl.ofl[k + 1], r1 * q1);
+  __syncthreads();
+  const double *X = C;  // (r, n, c1)
+  int c1 = r1;
+  if (q1) {
+    ro_gemm(r * n, q1, r1, [&](int i, int c) { return C[i * r1 + c]; }, [&](int c, int j) { return L[c * q1 + j]; },
+            [&](int i, int j, double v) { T[i * q1 + j] = v; });
+    __syncthreads();
+    X = T;
+    c1 = q1;
+  }
+  double *o = pl.out[k];
+  const int N = n * c1;
+  if (q) {
+    ro_gemm(q, N, r, [&](int i, int c) { return R[i * r + c]; }, [&](int c, int j) { return X[c * N + j]; },
+            [&](int i, int j, double v) { o[i * N + j] = v; });
+  } else {
+    for (int e = threadIdx.x; e < r * N; e += blockDim.x) o[e] = X[e];
+  }
+}
+
+template <class K>
+void ny_lds_attr(K kernel, int64_t shm) {
+  if (shm > 65536)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)shm);
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t ttk_nystroem_lds(int d, const int64_t *inner, const int64_t *ranks, const int64_t *lranks,
+                         const int64_t *rranks) {
+  const int64_t b = ny_plan(d, inner, ranks, lranks, rranks, nullptr, nullptr, nullptr);
+  return b < 0 ? -1 : b;
+}
+
+int ttk_nystroem(ttk_ctx ctx, int d, const double *const *cores, const int64_t *inner, const int64_t *ranks,
+                 const double *const *sk_left, const int64_t *lranks, const double *const *sk_right,
+                 const int64_t *rranks, double *const *out, int64_t *out_ranks) {
+  ttk::CtxScope scope(ctx);
+  hipStream_t st = ttk::ctx().stream;
+  NyPlan p;
+  int64_t shm[3] = {0, 0, 0}, words = 0;
+  const int64_t big =
+      (cores && sk_left && sk_right && out && out_ranks) ? ny_plan(d, inner, ranks, lranks, rranks, &p, shm, &words) : -2;
+  if (big == -2) {
+    ttk::set_error("ttk_nystroem: bad arguments (d >= 2, every rank and extent >= 1, equal boundary ranks)");
+    return TTK_ERR_ARG;
+  }
+  if (big < 0) {
+    ttk::set_error("ttk_nystroem: a core does not fit one workgroup's LDS (ttk_nystroem_lds)");
+    return TTK_ERR_ARG;
+  }
+  for (int k = 0; k < d; ++k) {
+    if (!cores[k] || !out[k] || (k + 1 < d && !sk_left[k]) || (k > 0 && !sk_right[k])) {
+      ttk::set_error("ttk_nystroem: null core %d", k);
+      return TTK_ERR_ARG;
+    }
+    p.core[k] = cores[k];
+    p.skl[k] = k + 1 < d ? sk_left[k] : nullptr;
+    p.skr[k] = k > 0 ? sk_right[k] : nullptr;
+    p.out[k] = out[k];
+  }
+  int pmax = 1;  // launch 2: one wave per Jacobi pair, up to 16 waves
+  for (int k = 1; k < d; ++k) pmax = p.q[k] > pmax ? p.q[k] : pmax;
+  const int nt2 = pmax <= 8 ? 256 : 1024;
+  void *w = nullptr;  // W_L, W_R, L, R of every bond: one stream-ordered block per call
+  TTK_HIP(hipMallocAsync(&w, (size_t)(words > 0 ? words : 2) * sizeof(double), st));
+  double *scr = static_cast<double *>(w);
+  ny_lds_attr(nystroem_sketch_kernel, shm[0]);
+  ny_lds_attr(nystroem_bond_kernel, shm[1]);
+  ny_lds_attr(nystroem_core_kernel, shm[2]);
+  hipError_t le = hipSuccess;
+  hipLaunchKernelGGL(nystroem_sketch_kernel, dim3(2), dim3(p.nt1), (size_t)shm[0], st, p, scr);
+  ttk::note_launch();
+  le = hipGetLastError();
+  if (le == hipSuccess) {
+    hipLaunchKernelGGL(nystroem_bond_kernel, dim3(d - 1), dim3(nt2), (size_t)shm[1], st, p, scr);
+    ttk::note_launch();
+    le = hipGetLastError();
+  }
+  if (le == hipSuccess) {
+    hipLaunchKernelGGL(nystroem_core_kernel, dim3(d), dim3(256), (size_t)shm[2], st, p, (const double *)scr);
+    ttk::note_launch();
+    le = hipGetLastError();
+  }
+  (void)hipFreeAsync(w, st);
+  if (le != hipSuccess) {
+    ttk::set_error("%s:%d launch: %s", __FILE__, __LINE__, hipGetErrorString(le));
+    return TTK_ERR_HIP;
+  }
+  for (int k = 0; k <= d; ++k) out_ranks[k] = p.q[k];
+  return TTK_OK;
+}
+
+}  // extern "C"

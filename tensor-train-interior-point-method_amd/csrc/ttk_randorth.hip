@@ -20,6 +20,7 @@
 
 #include "ttk_common.h"
 #include "ttk_internal.h"
+#include "ttk_tt_gemm.h"
 
 namespace {
 
@@ -118,22 +119,6 @@ int64_t ro_plan(int d, const int64_t *inner, const int64_t *ranks, const int64_t
     p->nt = work <= 2048 ? 256 : 1024;  // small trains: fewer waves at each barrier
   }
   return total * 8;
-}
-
-// C(i, j) = sum_k a(i, k) b(k, j), k ascending in one fma chain from 0; element e = i N + j goes to
-// thread e mod blockDim.x.
-template <class FA, class FB, class FC>
-__device__ __forceinline__ void ro_gemm(int M, int N, int K, FA a, FB b, FC store) {
-  for (int e = threadIdx.x; e < M * N; e += blockDim.x) {
-    const int i = e / N, j = e - i * N;
-    double acc = 0.0;
-    for (int k = 0; k < K; ++k) acc = fma(a(i, k), b(k, j), acc);
-    store(i, j, acc);
-  }
-}
-
-__device__ __forceinline__ void ro_load(double *dst, const double *src, int n) {
-  for (int e = threadIdx.x; e < n; e += blockDim.x) dst[e] = src[e];
 }
 
 // Householder QR of Y (m x n, column-major, in LDS) in place, any m and n: k = min(m, n) reflectors

@@ -562,6 +562,122 @@ def tt_rl_random_orthogonalise(tt, target_ranks):
     return tt
 
 
+# ------------------------------------------------------------------ generalised Nystroem rounding (`src/tt_ops.py:232-300`)
+def tt_sketch(shape, target_ranks):
+    """`src/tt_ops.py:240-244`: unnormalised scaled Gaussian cores (l_k, *shape, l_{k+1}) for the full
+    rank list `target_ranks` (boundaries included); host MT19937 draws, uploaded, no host read."""
+    return [D.from_numpy(np.divide(1, a * np.prod(shape) * b) * _rng.R().randn(a, *shape, b))
+            for a, b in zip(target_ranks[:-1], target_ranks[1:])]
+
+
+def tt_sketch_like(tt, target_ranks):
+    """`src/tt_ops.py:232-237`: `tt_sketch` with core i's middle extents taken from `tt[i]`."""
+    return [D.from_numpy(np.divide(1, a * np.prod(tt[i].shape[1:-1]) * b) * _rng.R().randn(a, *tt[i].shape[1:-1], b))
+            for i, (a, b) in enumerate(zip(target_ranks[:-1], target_ranks[1:]))]
+
+
+def nystroem_ranks(ranks, lranks, rranks):
+    """Rank list [r'_0, ..., r'_d] that `_tt_generalised_nystroem` gives a train with ranks `ranks` under
+    sketches with ranks `lranks` (left) and `rranks` (right), all d+1 entries with the boundaries: the
+    boundary ranks stay, an interior bond gets min(l_k, s_k), the length of S in the thin SVD of the
+    (l_k, s_k) matrix W_L W_R.  Host arithmetic only."""
+    d = len(ranks) - 1
+    return [int(ranks[0])] + [min(int(a), int(b)) for a, b in zip(lranks[1:d], rranks[1:d])] + [int(ranks[d])]
+
+
+NATIVE_NYSTROEM = os.environ.get("TTIPM_NATIVE_NYSTROEM", "1") == "1"
+
+
+def _nystroem_composed(tt, g1, g2):
+    """The rounding from D.einsum / D.matmul / D.svd: per bond a product, an SVD whose S is read on the
+    host, and the two factors; then one or two products per core.  Also what a train too large for
+    `ttk_nystroem` takes."""
+    d = len(tt)
+    Ls, Rs = [], []
+    for wl, wr in zip(tt_lr_contraction(tt, g1), tt_rl_contraction(tt, g2)):
+        U, _, Vt, s = D.svd(D.matmul(wl, wr))
+        with np.errstate(divide="ignore", invalid="ignore"):  # like the reference: no guard on S = 0
+            root_s_inv = D.from_numpy(np.diag(np.divide(1, np.sqrt(s))))
+        Ls.append(D.matmul(D.einsum("ik,jk->ij", wr, Vt), root_s_inv))
+        Rs.append(D.matmul(root_s_inv, D.einsum("ki,kj->ij", U, wl)))
+    out = []
+    for i, c in enumerate(tt):
+        sh = c.shape
+        x = D.contig(c)
+        if i < d - 1:
+            x = D.matmul(x.view(-1, sh[-1]), Ls[i])
+        if i > 0:
+            x = D.matmul(Rs[i - 1], x.view(sh[0], -1))
+        out.append(x.view(sh[0] if i == 0 else Rs[i - 1].shape[0], *sh[1:-1], sh[-1] if i == d - 1 else Ls[i].shape[1]))
+    return out
+
+
+def _nystroem_args(tt, g1, g2):
+    d = len(tt)
+    I64 = ctypes.c_int64
+    inner = (I64 * d)(*[_inner(c) for c in tt])
+    return (inner,) + tuple((I64 * (d + 1))(*([t[0].shape[0]] + [c.shape[-1] for c in t])) for t in (tt, g1, g2))
+
+
+def nystroem_lds(tt, g1, g2):
+    """The largest dynamic-LDS request (bytes) of `ttk_nystroem`'s launches for this train and these
+    sketches, -1 if some core does not fit one workgroup (the composed path then runs)."""
+    return int(D.lib.ttk_nystroem_lds(len(tt), *_nystroem_args(tt, g1, g2)))
+
+
+def _nystroem_native(tt, g1, g2, args):
+    """`ttk_nystroem`: three launches of independent workgroups into one fresh buffer (the output cores
+    are views of it).  No host read: the ranks come from `nystroem_ranks`.  `args`: `_nystroem_args`."""
+    d = len(tt)
+    inner, ranks, lranks, rranks = args
+    rk = nystroem_ranks(ranks, lranks, rranks)
+    cs, s1, s2 = ([D.contig(c) for c in t] for t in (tt, g1, g2))
+    sizes = [rk[k] * inner[k] * rk[k + 1] for k in range(d)]
+    offs = np.concatenate(([0], np.cumsum([(s + 1) & ~1 for s in sizes])))  # 16-byte aligned cores
+    buf = D.empty(int(offs[-1]))
+    outs = [buf[int(offs[k]):int(offs[k]) + sizes[k]] for k in range(d)]
+    P = ctypes.c_void_p
+    ptrs = lambda ts: (P * d)(*[t.data_ptr() for t in ts])  # noqa: E731
+    got = (ctypes.c_int64 * (d + 1))()
+    D._stream()
+    D.check(D.lib.ttk_nystroem(D.ctx(), d, ptrs(cs), inner, ranks, ptrs(s1), lranks, ptrs(s2), rranks, ptrs(outs), got),
+            "nystroem")
+    assert list(got) == rk, (list(got), rk)
+    return [o.view(rk[k], *tt[k].shape[1:-1], rk[k + 1]) for k, o in enumerate(outs)]
+
+
+def _tt_generalised_nystroem(tt, g1, g2):
+    """`src/tt_ops.py:273-292`: with W_L = tt_lr_contraction(tt, g1) and W_R = tt_rl_contraction(tt, g2),
+    per bond P = W_L W_R = U diag(S) V^T (thin), L = W_R V diag(1/sqrt(S)), R = diag(1/sqrt(S)) U^T W_L;
+    core i <- R_i core_i L_{i+1} (no R on the first core, no L on the last).  The output ranks are
+    `nystroem_ranks` (fixed by the sketches' ranks, no truncation decision); like the reference, a zero
+    singular value is not guarded.  The caller's tensors are never written; the list is rebound in
+    place, like the reference's list mutation.  Three launches without a host read (`ttk_nystroem`)
+    when every core fits one workgroup's LDS, else composed from einsum / SVD calls with S read on
+    the host (TTIPM_NATIVE_NYSTROEM=0: always composed)."""
+    if len(tt) < 2:
+        return tt
+    out = None
+    if NATIVE_NYSTROEM and D.DEV.type == "cuda" and hasattr(D.lib, "ttk_nystroem"):
+        args = _nystroem_args(tt, g1, g2)  # built once for the fit check and the call
+        if D.lib.ttk_nystroem_lds(len(tt), *args) >= 0:
+            out = _nystroem_native(tt, g1, g2, args)
+    tt[:] = out if out is not None else _nystroem_composed(tt, g1, g2)
+    return tt
+
+
+def tt_generalised_nystroem(tt, target_ranks):
+    """`src/tt_ops.py:295-300`: rounding to the given bond ranks with two fresh Gaussian sketches, the
+    left one with `target_ranks` and then the right one with every rank one larger
+    (`tt_random_gaussian`: host MT19937 draws and one host read each for the normalisation)."""
+    if len(tt) > 1:
+        shape = tuple(tt[0].shape[1:-1])
+        g1 = tt_random_gaussian(target_ranks, shape=shape)
+        g2 = tt_random_gaussian([r + 1 for r in target_ranks], shape=shape)
+        return _tt_generalised_nystroem(tt, g1, g2)
+    return tt
+
+
 # ------------------------------------------------------------------ zip-up products (`:391-502`)
 def swap_cores(a, b, eps):
     """`cy_src/tt_ops_cy.pyx:393-426`"""
