@@ -561,6 +561,33 @@ int ttk_nystroem(ttk_ctx ctx, int d, const double *const *cores, const int64_t *
                  const double *const *sk_left, const int64_t *lranks, const double *const *sk_right,
                  const int64_t *rranks, double *const *out, int64_t *out_ranks);
 
+/* Deterministic fixed-rank TT retraction in one launch (`tt_rank_retraction`, src/tt_ops.py:132-152):
+ * one workgroup first walks right to left, k = d-1 .. 1: Householder QR of the transposed carried core
+ * (n_k rho_{k+1} x r_k; LAPACK's sign convention, m < n handled), Q^T is the orthogonalised core k
+ * (rho_k, n_k, rho_{k+1}), kept in one stream-ordered scratch block, and core k-1 <- core_{k-1} R^T stays
+ * in LDS; then left to right, i = 0 .. d-2: one-sided Jacobi SVD of the carried core Z (q_i n_i x
+ * rho_{i+1}) on the rows of whichever of Z or Z^T has fewer (fixed pair order, at most 30 sweeps, S sorted
+ * descending, ties by index), out_i = U[:, :q_{i+1}], carried <- diag(S) V^T[:q_{i+1}] x orthogonalised
+ * core i+1; the last carried core is out_{d-1}.  No sketch, no truncation decision and no host read:
+ * the output ranks are host arithmetic, rho_d = 1, rho_k = min(inner[k] rho_{k+1}, ranks[k]);
+ * out_ranks[0] = 1, out_ranks[i+1] = min(upper[i], out_ranks[i] inner[i], rho_{i+1}), out_ranks[d] = 1,
+ * and the call returns after enqueueing.  The reference also moves a scalar into the last core: the
+ * gauge differs, the represented tensor does not.  A singular value that is exactly 0 gives zero
+ * vectors: nothing divides by it, and the all-zero train comes back finite.  Fixed summation and
+ * rotation order: two calls on the same input give the same bits.
+ * cores[k]: device, contiguous (ranks[k], inner[k], ranks[k+1]) fp64, read only; ranks[0] == ranks[d]
+ * == 1; upper: d-1 entries, the largest rank each interior bond may keep; out[k]: caller-owned
+ * contiguous buffers of out_ranks[k] inner[k] out_ranks[k+1] doubles that overlap no input; ranks,
+ * out_ranks: d+1 entries.  ttk_retract_lds: the bytes of LDS the sweep needs (one step's working set,
+ * not the train), or -1 when it does not fit one workgroup (at most 160 KiB and 32 cores) or the
+ * arguments are invalid -- the caller then composes the retraction from ttk_qr, ttk_svd and
+ * ttk_einsum.  ttk_retract validates on the host (d >= 2, every rank, extent and upper >= 1,
+ * boundary ranks 1, no null pointer, the LDS fit) and returns TTK_ERR_ARG without launching when a
+ * check fails. */
+int64_t ttk_retract_lds(int d, const int64_t *inner, const int64_t *ranks, const int64_t *upper);
+int ttk_retract(ttk_ctx ctx, int d, const double *const *cores, const int64_t *inner, const int64_t *ranks,
+                const int64_t *upper, double *const *out, int64_t *out_ranks);
+
 /* Dense Schur-complement local KKT solve in one call (SURVEY §8(b) `ttk_local_assemble` +
  * `ttk_dense_schur_solve`; the dense branch of `_ipm_local_solver`, src/tt_ipm.py:183-229):
  * assembles L_XI = B22 diag(inv_I), L_eq = B01, L_Z = B21 (each 'lsr,smnS,LSR->lmLrnR'), Cholesky of

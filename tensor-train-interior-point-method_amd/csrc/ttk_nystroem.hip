@@ -37,9 +37,6 @@ namespace {
 
 constexpr int NY_MAXD = 32;                  // cores per train (the plan travels as a kernel argument)
 constexpr int64_t NY_LDS_MAX = 160 * 1024;   // bytes one workgroup may declare
-constexpr int NY_SWEEPS = 30;                // hard cap of the Jacobi sweeps (they converge in under 10)
-constexpr int NY_FLAGS = 16;                 // doubles that hold the NY_SWEEPS per-sweep rotation flags
-constexpr double NY_EPS = 2.220446049250313e-16;
 
 struct NyPlan {
   int d, nt1;
@@ -206,49 +203,6 @@ __global__ __launch_bounds__(1024) void nystroem_sketch_kernel(const NyPlan p, d
       __syncthreads();
     }
   }
-}
-
-// One sweep-round of the one-sided Jacobi on the rows of A (p x n) with the rotations accumulated in
-// G (p x p): the round's disjoint pairs (circle method over m = p rounded up to even players, the
-// last one fixed) go to the waves in turn.  A pair (i, j) is rotated when |<a_i, a_j>| exceeds
-// tol ||a_i|| ||a_j||.  Returns after a workgroup barrier.
-__device__ void ny_jacobi_round(double *A, double *G, int p, int n, int m, int round, double tol2, int *flag) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  for (int t = wid; t < m / 2; t += nw) {
-    int i = t == 0 ? m - 1 : (round + t) % (m - 1);
-    int j = (round - t + (m - 1)) % (m - 1);
-    if (i > j) {
-      const int x = i;
-      i = j, j = x;
-    }
-    if (j >= p) continue;  // the bye of an odd p
-    double *ai = A + i * n, *aj = A + j * n;
-    double pa = 0.0, pb = 0.0, pg = 0.0;
-    for (int c = lane; c < n; c += 64) {
-      const double x = ai[c], y = aj[c];
-      pa = fma(x, x, pa);
-      pb = fma(y, y, pb);
-      pg = fma(x, y, pg);
-    }
-    const double al = ttk::wave_sum(pa), be = ttk::wave_sum(pb), ga = ttk::wave_sum(pg);
-    if (!(ga * ga > tol2 * al * be)) continue;  // |ga| <= tol sqrt(al be): orthogonal already
-    const double zeta = (be - al) / (2.0 * ga);
-    const double tn = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-    const double cs = 1.0 / sqrt(1.0 + tn * tn), sn = cs * tn;
-    for (int c = lane; c < n; c += 64) {
-      const double x = ai[c], y = aj[c];
-      ai[c] = cs * x - sn * y;
-      aj[c] = sn * x + cs * y;
-    }
-    double *gi = G + i * p, *gj = G + j * p;
-    for (int c = lane; c < p; c += 64) {
-      const double x = gi[c], y = gj[c];
-      gi[c] = cs * x - sn * y;
-      gj[c] = sn * x + cs * y;
-    }
-    if (lane == 0) *flag = 1;
-  }
-  __syncthreads();
 }
 
 // ---- launch 2: workgroup b owns bond k = b + 1

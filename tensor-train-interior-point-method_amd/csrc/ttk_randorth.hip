@@ -121,81 +121,6 @@ int64_t ro_plan(int d, const int64_t *inner, const int64_t *ranks, const int64_t
   return total * 8;
 }
 
-// Householder QR of Y (m x n, column-major, in LDS) in place, any m and n: k = min(m, n) reflectors
-// v_j = [1; Y[j+1:, j]] with tau[j], R in the upper trapezoid.  LAPACK's sign convention (dlarfg):
-// beta = -sign(alpha) ||x||, tau = (beta - alpha) / beta, and a column that is zero below the
-// diagonal gives tau = 0 (H = I).  Every wave forms reflector j itself (the same wave-tree sum of the
-// same lane partials, so the same bits in every wave) and applies it to the columns it owns: one
-// workgroup barrier per column.  Ends with a barrier.
-__device__ void ro_householder(double *Y, int m, int n, double *tau) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  const int k = m < n ? m : n;
-  for (int j = 0; j < k; ++j) {
-    double *wj = Y + j * m;
-    double part = 0.0;
-    for (int i = j + 1 + lane; i < m; i += 64) part = fma(wj[i], wj[i], part);
-    const double s2 = ttk::wave_sum(part);
-    const double alpha = wj[j];
-    double tj, sc, beta;
-    if (s2 == 0.0) {
-      tj = 0.0;
-      beta = alpha;
-      sc = 0.0;
-    } else {
-      const double nrm = sqrt(alpha * alpha + s2);
-      beta = (alpha >= 0.0) ? -nrm : nrm;
-      tj = (beta - alpha) / beta;
-      sc = 1.0 / (alpha - beta);
-    }
-    if (tj != 0.0) {
-      for (int c = j + 1 + wid; c < n; c += nw) {
-        double *wc = Y + c * m;
-        double dp = (lane == 0) ? wc[j] : 0.0;
-        for (int i = j + 1 + lane; i < m; i += 64) dp = fma(wj[i] * sc, wc[i], dp);
-        const double dd = ttk::wave_sum(dp) * tj;
-        if (lane == 0) wc[j] -= dd;
-        for (int i = j + 1 + lane; i < m; i += 64) wc[i] -= dd * (wj[i] * sc);
-      }
-    }
-    __syncthreads();
-    if (wid == j % nw) {  // every wave has read column j; nobody reads it again before the loop ends
-      for (int i = j + 1 + lane; i < m; i += 64) wj[i] *= sc;
-      if (lane == 0) {
-        wj[j] = beta;
-        tau[j] = tj;
-      }
-    }
-  }
-  __syncthreads();
-}
-
-// Qc (m x k, column-major, in LDS) = H_0 ... H_{k-1} [I_k; 0] from the reflectors ro_householder left
-// in Y.  Column c only meets the reflectors j = c, c-1, ..., 0, so a wave takes whole columns through
-// all their reflectors with no workgroup barrier in between.  Ends with a barrier.
-__device__ void ro_form_q(const double *Y, const double *tau, int m, int k, double *Qc) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  for (int e = threadIdx.x; e < m * k; e += blockDim.x) {
-    const int c = e / m, i = e - c * m;
-    Qc[e] = (i == c) ? 1.0 : 0.0;
-  }
-  __syncthreads();
-  for (int c = wid; c < k; c += nw) {
-    double *qc = Qc + c * m;
-    for (int j = c; j >= 0; --j) {
-      const double tj = tau[j];
-      if (tj == 0.0) continue;
-      const double *v = Y + j * m;
-      double dp = (lane == 0) ? qc[j] : 0.0;
-      for (int i = j + 1 + lane; i < m; i += 64) dp = fma(v[i], qc[i], dp);
-      const double dd = ttk::wave_sum(dp) * tj;
-      if (lane == 0) qc[j] -= dd;
-      for (int i = j + 1 + lane; i < m; i += 64) qc[i] -= dd * v[i];
-      __threadfence_block();  // one wave's LDS accesses stay in program order behind the fence
-    }
-  }
-  __syncthreads();
-}
-
 __global__ __launch_bounds__(1024) void rand_orth_kernel(const RoPlan p, double *wscr) {
   extern __shared__ __attribute__((aligned(16))) double ro_lds[];
   double *Z = ro_lds + p.oZ, *C = ro_lds + p.oC, *Y = ro_lds + p.oY, *Qc = ro_lds + p.oQ, *Mq = ro_lds + p.oM,

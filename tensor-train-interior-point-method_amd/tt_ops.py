@@ -390,8 +390,71 @@ def tt_mask_rank_reduce(tt, mask, eps=1e-18):
     return tt_add(tt, [D.scaled(c, factor) for c in mask])
 
 
+def retraction_ranks(inner, ranks, upper):
+    """Rank list [q_0, ..., q_d] that `tt_rank_retraction` gives a train with middle extents `inner` (d
+    entries) and ranks `ranks` (d+1 entries, boundaries 1) under the bounds `upper` (d-1 entries): the QR
+    sweep leaves rho_d = 1, rho_k = min(inner_k rho_{k+1}, ranks_k), and the SVD sweep keeps q_0 = 1,
+    q_{i+1} = min(upper_i, q_i inner_i, rho_{i+1}) (`len(abs_S > 0)` is `len(S)`).  Host arithmetic only."""
+    d = len(inner)
+    rho = [1] * (d + 1)
+    for k in range(d - 1, 0, -1):
+        rho[k] = min(int(inner[k]) * rho[k + 1], int(ranks[k]))
+    q = [1] * (d + 1)
+    for i in range(d - 1):
+        q[i + 1] = min(int(upper[i]), q[i] * int(inner[i]), rho[i + 1])
+    return q
+
+
+NATIVE_RETRACT = os.environ.get("TTIPM_NATIVE_RETRACT", "0") == "1"
+
+
+def _retract_args(tt, upper):
+    d = len(tt)
+    I64 = ctypes.c_int64
+    inner = (I64 * d)(*[int(np.prod(c.shape[1:-1])) for c in tt])
+    ranks = (I64 * (d + 1))(*([tt[0].shape[0]] + [c.shape[-1] for c in tt]))
+    return inner, ranks, (I64 * max(d - 1, 1))(*[int(u) for u in upper])
+
+
+def retract_lds(tt, upper):
+    """Bytes of LDS `ttk_retract` needs for this train under the bounds `upper` (d-1 entries), -1 if it
+    does not fit one workgroup (the composed path then runs)."""
+    if len(tt) < 2 or len(upper) != len(tt) - 1:
+        return -1
+    return int(D.lib.ttk_retract_lds(len(tt), *_retract_args(tt, upper)))
+
+
+def _retract_native(tt, upper):
+    """`ttk_retract`: the QR sweep and the Jacobi-SVD sweep in one launch of one workgroup, into one
+    fresh buffer (the output cores are views of it).  No host read: the ranks come from
+    `retraction_ranks`."""
+    d = len(tt)
+    inner, ranks, ub = _retract_args(tt, upper)
+    rk = retraction_ranks(inner, ranks, ub)
+    cs = [D.contig(c) for c in tt]
+    sizes = [rk[k] * inner[k] * rk[k + 1] for k in range(d)]
+    offs = np.concatenate(([0], np.cumsum([(s + 1) & ~1 for s in sizes])))  # 16-byte aligned cores
+    buf = D.empty(int(offs[-1]))
+    outs = [buf[int(offs[k]):int(offs[k]) + sizes[k]] for k in range(d)]
+    P = ctypes.c_void_p
+    got = (ctypes.c_int64 * (d + 1))()
+    D._stream()
+    D.check(D.lib.ttk_retract(D.ctx(), d, (P * d)(*[c.data_ptr() for c in cs]), inner, ranks, ub,
+                              (P * d)(*[o.data_ptr() for o in outs]), got), "retract")
+    assert list(got) == rk, (list(got), rk)
+    return [o.view(rk[k], *tt[k].shape[1:-1], rk[k + 1]) for k, o in enumerate(outs)]
+
+
 def tt_rank_retraction(tt, upper_ranks):
-    """`src/tt_ops.py:132-152` (argpartition top-k on the host singular values)."""
+    """`src/tt_ops.py:132-152` (argpartition top-k on the host singular values).  With
+    TTIPM_NATIVE_RETRACT=1, on the GPU, with one bound per interior bond and a train that fits
+    (`retract_lds`): one launch without a host read (`ttk_retract`), the same tensor in another gauge;
+    the caller's tensors are never written and the list is rebound in place.  Off by default: the
+    whole-solve goldens are pinned to the composed path's arithmetic."""
+    if (NATIVE_RETRACT and D.DEV.type == "cuda" and len(tt) > 1 and len(upper_ranks) == len(tt) - 1
+            and retract_lds(tt, upper_ranks) >= 0):
+        tt[:] = _retract_native(tt, upper_ranks)
+        return tt
     tt = tt_rl_orthogonalise_py(tt)
     rank = 1
     for idx, up in enumerate(upper_ranks):
