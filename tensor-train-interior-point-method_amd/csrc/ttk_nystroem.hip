@@ -35,118 +35,79 @@
 
 namespace {
 
-constexpr int NY_MAXD = 32;                  // cores per train (the plan travels as a kernel argument)
-constexpr int64_t NY_LDS_MAX = 160 * 1024;   // bytes one workgroup may declare
-
 struct NyPlan {
-  int d, nt1;
-  int n[NY_MAXD];       // middle extents
-  int r[NY_MAXD + 1];   // train bond ranks
-  int l[NY_MAXD + 1];   // left sketch bond ranks
-  int s[NY_MAXD + 1];   // right sketch bond ranks
-  int q[NY_MAXD + 1];   // output bond ranks
-  int owl[NY_MAXD], owr[NY_MAXD], ofl[NY_MAXD], ofr[NY_MAXD];  // W_L, W_R, L, R of bond k in the scratch block
+  int d, nt1, nt2;      // threads of launches 1 and 2
+  int n[TT_MAXD];       // middle extents
+  int r[TT_MAXD + 1];   // train bond ranks
+  int l[TT_MAXD + 1];   // left sketch bond ranks
+  int s[TT_MAXD + 1];   // right sketch bond ranks
+  int q[TT_MAXD + 1];   // output bond ranks
+  int owl[TT_MAXD], owr[TT_MAXD], ofl[TT_MAXD], ofr[TT_MAXD];  // W_L, W_R, L, R of bond k in the scratch block
   int oC, oZ, oY, oW;   // launch 1's LDS regions (offsets in doubles, all even: 16-byte aligned)
-  const double *core[NY_MAXD];
-  const double *skl[NY_MAXD];
-  const double *skr[NY_MAXD];
-  double *out[NY_MAXD];
+  const double *core[TT_MAXD];
+  const double *skl[TT_MAXD];
+  const double *skr[TT_MAXD];
+  double *out[TT_MAXD];
 };
 
-__host__ __device__ inline int64_t ny_even(int64_t v) { return (v + 1) & ~(int64_t)1; }
-
 // doubles of LDS launch 2 needs for a bond with W_L (l x r) and W_R (r x s)
-__host__ __device__ inline int64_t ny_bond_words(int64_t l, int64_t r, int64_t s) {
+inline int64_t ny_bond_words(int64_t l, int64_t r, int64_t s) {
   const int64_t p = l < s ? l : s;
-  return ny_even(l * r) + ny_even(r * s) + ny_even(l * s) + ny_even(p * p) + 2 * ny_even(p) + NY_FLAGS;
+  return tt_even(l * r) + tt_even(r * s) + tt_even(l * s) + tt_even(p * p) + 2 * tt_even(p) + NY_FLAGS;
 }
 
 // doubles of LDS launch 3 needs for a core (r, n, r1) with R (q x r) and L (r1 x q1); q = 0 / q1 = 0:
 // the first / last core, which has no such factor
-__host__ __device__ inline int64_t ny_core_words(int64_t q, int64_t r, int64_t n, int64_t r1, int64_t q1) {
-  return ny_even(r * n * r1) + ny_even(q * r) + ny_even(r1 * q1) + ny_even(r * n * q1);
+inline int64_t ny_core_words(int64_t q, int64_t r, int64_t n, int64_t r1, int64_t q1) {
+  return tt_even(r * n * r1) + tt_even(q * r) + tt_even(r1 * q1) + tt_even(r * n * q1);
 }
 
 // Validates the extents and lays out scratch and LDS.  Returns the largest dynamic-LDS request of the
 // three launches in bytes, -1 when some core does not fit one workgroup (or the train has more than
-// NY_MAXD cores), -2 on invalid arguments.  shm[3]: bytes per launch; *words: doubles of scratch.
+// TT_MAXD cores), -2 on invalid arguments.  shm[3]: bytes per launch; *words: doubles of scratch.
 int64_t ny_plan(int d, const int64_t *inner, const int64_t *ranks, const int64_t *lranks, const int64_t *rranks,
                 NyPlan *p, int64_t *shm, int64_t *words) {
-  if (d < 2 || !inner || !ranks || !lranks || !rranks) return -2;
-  for (int k = 0; k <= d; ++k)
-    if (ranks[k] < 1 || lranks[k] < 1 || rranks[k] < 1) return -2;
-  for (int k = 0; k < d; ++k)
-    if (inner[k] < 1) return -2;
-  if (ranks[0] != lranks[0] || ranks[0] != rranks[0] || ranks[d] != lranks[d] || ranks[d] != rranks[d]) return -2;
-  if (d > NY_MAXD) return -1;
-  const int64_t cap = NY_LDS_MAX / 8;  // no single extent or product may pass the LDS capacity
-  for (int k = 0; k <= d; ++k)
-    if (ranks[k] > cap || lranks[k] > cap || rranks[k] > cap) return -1;
-  for (int k = 0; k < d; ++k)
-    if (inner[k] > cap) return -1;
+  const int chk = tt_check_extents(d, inner, {ranks, lranks, rranks});
+  if (chk == -2 || ranks[0] != lranks[0] || ranks[0] != rranks[0] || ranks[d] != lranks[d] || ranks[d] != rranks[d])
+    return -2;
+  if (chk) return chk;
   const int64_t *n = inner, *r = ranks, *l = lranks, *s = rranks;
-  bool over = false;
-  auto p3 = [&](int64_t a, int64_t b, int64_t c) {  // a b c, saturating at cap + 1 (factors <= cap: no overflow)
-    int64_t v = a * b;
-    v = v > cap ? cap + 1 : v * c;
-    if (v > cap) over = true, v = cap + 1;
-    return v;
-  };
+  TtLayout L, S;  // launch 1's LDS, scratch
   // launch 1: the core, the sketch core, the intermediate and the running W of either chain
-  int64_t zC = 2, zZ = 2, zY = 2, zW = 2;
-  auto up = [](int64_t &z, int64_t v) { z = v > z ? v : z; };
-  for (int k = 0; k < d; ++k) up(zC, p3(r[k], n[k], r[k + 1]));
-  for (int k = 1; k < d; ++k) up(zZ, p3(s[k], n[k], s[k + 1]));
-  for (int k = 0; k + 1 < d; ++k) up(zZ, p3(l[k], n[k], l[k + 1]));
+  int64_t zC = 2, zZ = 2, zY = 2, zW = 2, b2 = 0, b3 = 0, pmax = 1;
+  for (int k = 0; k < d; ++k) L.up(zC, r[k], n[k], r[k + 1]);
+  for (int k = 1; k < d; ++k) L.up(zZ, s[k], n[k], s[k + 1]);
+  for (int k = 0; k + 1 < d; ++k) L.up(zZ, l[k], n[k], l[k + 1]);
   for (int k = 1; k + 1 < d; ++k) {
-    up(zY, p3(r[k], n[k], s[k + 1]));
-    up(zY, p3(l[k], n[k], r[k + 1]));
+    L.up(zY, r[k], n[k], s[k + 1]);
+    L.up(zY, l[k], n[k], r[k + 1]);
   }
-  if (over) return -1;
-  int64_t w = 0, b2 = 0, b3 = 0;
+  for (int k = 0; k <= d; ++k) {
+    p->r[k] = (int)r[k], p->l[k] = (int)l[k], p->s[k] = (int)s[k];
+    p->q[k] = (int)(k == 0 || k == d ? r[k] : (l[k] < s[k] ? l[k] : s[k]));
+  }
   for (int k = 1; k < d; ++k) {
-    const int64_t lr = p3(l[k], r[k], 1), rs = p3(r[k], s[k], 1), ls = p3(l[k], s[k], 1);
-    up(zW, lr);
-    up(zW, rs);
-    if (over) return -1;
-    if (p) {
-      p->owl[k] = (int)w, p->owr[k] = (int)(w + ny_even(lr));
-      p->ofl[k] = (int)(w + ny_even(lr) + ny_even(rs)), p->ofr[k] = (int)(w + ny_even(lr) + 2 * ny_even(rs));
-    }
-    w += ny_even(lr) + 2 * ny_even(rs) + ny_even(lr);  // W_L, W_R, L (r x q <= r x s), R (q x r <= l x r)
-    if (w > ((int64_t)1 << 30)) return -1;
-    up(b2, ny_bond_words(l[k], r[k], s[k]));
+    const int64_t lr = L.mul(l[k], r[k]), rs = L.mul(r[k], s[k]);
+    L.up(zW, lr);
+    L.up(zW, rs);
+    L.up(b2, ny_bond_words(l[k], r[k], s[k]));
+    L.up(pmax, p->q[k]);
+    // W_L, W_R, L (r x q <= r x s), R (q x r <= l x r)
+    p->owl[k] = S.take(lr), p->owr[k] = S.take(rs), p->ofl[k] = S.take(rs), p->ofr[k] = S.take(lr);
   }
   for (int k = 0; k < d; ++k) {
-    const int64_t q = k > 0 ? (l[k] < s[k] ? l[k] : s[k]) : 0;
-    const int64_t q1 = k + 1 < d ? (l[k + 1] < s[k + 1] ? l[k + 1] : s[k + 1]) : 0;
-    p3(r[k], n[k], q1 > 0 ? q1 : 1);
-    if (over) return -1;
-    up(b3, ny_core_words(q, r[k], n[k], r[k + 1], q1));
+    const int64_t q = k > 0 ? p->q[k] : 0, q1 = k + 1 < d ? p->q[k + 1] : 0;
+    L.up(b3, ny_core_words(q, r[k], n[k], r[k + 1], q1));
   }
-  if (over) return -1;
-  const int64_t b1 = ny_even(zC) + ny_even(zZ) + ny_even(zY) + ny_even(zW);
-  int64_t big = b1 > b2 ? b1 : b2;
-  big = big > b3 ? big : b3;
-  if (big * 8 > NY_LDS_MAX) return -1;
-  if (shm) shm[0] = b1 * 8, shm[1] = b2 * 8, shm[2] = b3 * 8;
-  if (words) *words = w;
-  if (p) {
-    p->d = d;
-    for (int k = 0; k < d; ++k) p->n[k] = (int)n[k];
-    for (int k = 0; k <= d; ++k) {
-      p->r[k] = (int)r[k];
-      p->l[k] = (int)l[k];
-      p->s[k] = (int)s[k];
-      p->q[k] = (int)(k == 0 || k == d ? r[k] : (l[k] < s[k] ? l[k] : s[k]));
-    }
-    int64_t o = 0;
-    p->oC = (int)o, o += ny_even(zC);
-    p->oZ = (int)o, o += ny_even(zZ);
-    p->oY = (int)o, o += ny_even(zY);
-    p->oW = (int)o;
-    p->nt1 = (zY > zC ? zY : zC) <= 2048 ? 256 : 1024;  // small trains: fewer waves at each barrier
-  }
+  p->oC = L.take(zC), p->oZ = L.take(zZ), p->oY = L.take(zY), p->oW = L.take(zW);
+  const int64_t b1 = L.words, big = b1 > b2 ? (b1 > b3 ? b1 : b3) : (b2 > b3 ? b2 : b3);
+  if (L.over || big * 8 > TT_LDS_MAX) return -1;
+  shm[0] = b1 * 8, shm[1] = b2 * 8, shm[2] = b3 * 8;
+  *words = S.words;
+  p->d = d;
+  for (int k = 0; k < d; ++k) p->n[k] = (int)n[k];
+  p->nt1 = tt_threads(zY > zC ? zY : zC, 1);
+  p->nt2 = tt_threads(0, pmax);
   return big * 8;
 }
 
@@ -157,27 +118,9 @@ __global__ __launch_bounds__(1024) void nystroem_sketch_kernel(const NyPlan p, d
   const int d = p.d;
   if (blockIdx.x == 0) {
     // right to left: W_R[k] (r_k x s_k) = unfold(A_k W_R[k+1]) (r_k x n s_{k+1}) unfold(B_k)^T
-    for (int k = d - 1; k >= 1; --k) {
-      const int rk = p.r[k], n = p.n[k], r1 = p.r[k + 1], sk = p.s[k], s1 = p.s[k + 1];
-      ro_load(C, p.core[k], rk * n * r1);
-      ro_load(Z, p.skr[k], sk * n * s1);
-      __syncthreads();
-      const double *T = C;  // the last core meets its sketch core directly (r_d == s_d)
-      if (k < d - 1) {
-        ro_gemm(rk * n, s1, r1, [&](int i, int c) { return C[i * r1 + c]; }, [&](int c, int j) { return W[c * s1 + j]; },
-                [&](int i, int j, double v) { Y[i * s1 + j] = v; });
-        __syncthreads();
-        T = Y;
-      }
-      const int K = n * s1;
-      double *wk = scr + p.owr[k];
-      ro_gemm(rk, sk, K, [&](int i, int c) { return T[i * K + c]; }, [&](int c, int j) { return Z[j * K + c]; },
-              [&](int i, int j, double v) {
-                W[i * sk + j] = v;
-                wk[i * sk + j] = v;
-              });
-      __syncthreads();
-    }
+    for (int k = d - 1; k >= 1; --k)  // the last core meets its sketch core directly (r_d == s_d)
+      tt_sketch_step(p.core[k], p.skr[k], p.r[k], p.n[k], p.r[k + 1], p.s[k], p.s[k + 1], k == d - 1, C, Z, Y, W,
+                     scr + p.owr[k]);
   } else {
     // left to right: W_L[k+1] (l_{k+1} x r_{k+1}) = unfold(G_k)^T (l_{k+1} x l_k n) unfold(W_L[k] A_k)
     for (int k = 0; k + 1 < d; ++k) {
@@ -212,41 +155,15 @@ __global__ __launch_bounds__(1024) void nystroem_bond_kernel(const NyPlan pl, do
   const int l = pl.l[k], r = pl.r[k], s = pl.s[k];
   const bool rows = l <= s;  // rotate the rows of P, else those of P^T
   const int p = rows ? l : s, n = rows ? s : l;
-  double *WL = ny_lds, *WR = WL + ny_even(l * r), *A = WR + ny_even(r * s), *G = A + ny_even(l * s);
-  double *sv = G + ny_even(p * p);
-  int *perm = reinterpret_cast<int *>(sv + ny_even(p));
-  int *flag = reinterpret_cast<int *>(sv + 2 * ny_even(p));
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  double *WL = ny_lds, *WR = WL + tt_even(l * r), *A = WR + tt_even(r * s), *G = A + tt_even(l * s);
+  double *sv = G + tt_even(p * p);
   ro_load(WL, scr + pl.owl[k], l * r);
   ro_load(WR, scr + pl.owr[k], r * s);
-  for (int e = threadIdx.x; e < p * p; e += blockDim.x) G[e] = (e / p == e % p) ? 1.0 : 0.0;
-  for (int e = threadIdx.x; e < NY_SWEEPS; e += blockDim.x) flag[e] = 0;
-  for (int e = threadIdx.x; e < p; e += blockDim.x) perm[e] = e;  // stays a valid index whatever the sort meets
   __syncthreads();
   // A = P (l x s) or P^T (s x l), P = W_L W_R
   ro_gemm(l, s, r, [&](int i, int c) { return WL[i * r + c]; }, [&](int c, int j) { return WR[c * s + j]; },
           [&](int i, int j, double v) { A[rows ? i * s + j : j * l + i] = v; });
-  __syncthreads();
-  const double tol = NY_EPS * (n > 16 ? (double)n : 16.0), tol2 = tol * tol;
-  const int m = (p + 1) & ~1;
-  for (int sweep = 0; sweep < NY_SWEEPS && p > 1; ++sweep) {
-    for (int round = 0; round < m - 1; ++round) ny_jacobi_round(A, G, p, n, m, round, tol2, flag + sweep);
-    if (flag[sweep] == 0) break;  // written before the round's barrier: every thread reads the same value
-  }
-  // sigma_j = ||row j||, sorted descending (ties by index): perm[position] = row
-  for (int j = wid; j < p; j += nw) {
-    double part = 0.0;
-    for (int c = lane; c < n; c += 64) part = fma(A[j * n + c], A[j * n + c], part);
-    const double nrm = sqrt(ttk::wave_sum(part));
-    if (lane == 0) sv[j] = nrm;
-  }
-  __syncthreads();
-  for (int j = threadIdx.x; j < p; j += blockDim.x) {
-    int pos = 0;
-    for (int i = 0; i < p; ++i) pos += (sv[i] > sv[j] || (sv[i] == sv[j] && i < j)) ? 1 : 0;
-    perm[pos < p ? pos : p - 1] = j;  // a NaN compares false everywhere: stay in bounds
-  }
-  __syncthreads();
+  const int *perm = tt_jacobi_svd(A, G, sv, p, n);
   // rows: G = U^T, A = diag(S) V^T:   R = diag(S^-1/2) G W_L,    L = W_R A^T diag(S^-3/2)
   // else: G = V^T, A = diag(S) U^T:   L = W_R G^T diag(S^-1/2),  R = diag(S^-3/2) A W_L
   double *Lk = scr + pl.ofl[k], *Rk = scr + pl.ofr[k];
@@ -269,7 +186,7 @@ __global__ __launch_bounds__(1024) void nystroem_core_kernel(const NyPlan pl, co
   const int k = blockIdx.x, d = pl.d;
   const int r = pl.r[k], n = pl.n[k], r1 = pl.r[k + 1];
   const int q = k > 0 ? pl.q[k] : 0, q1 = k + 1 < d ? pl.q[k + 1] : 0;
-  double *C = ny_lds, *R = C + ny_even(r * n * r1), *L = R + ny_even(q * r), *T = L + ny_even(r1 * q1);
+  double *C = ny_lds, *R = C + tt_even(r * n * r1), *L = R + tt_even(q * r), *T = L + tt_even(r1 * q1);
   ro_load(C, pl.core[k], r * n * r1);
   if (q) ro_load(R, scr + pl.ofr[k], q * r);
   if (q1) ro_load(L, scr + pl.ofl[k + 1], r1 * q1);
@@ -293,20 +210,15 @@ __global__ __launch_bounds__(1024) void nystroem_core_kernel(const NyPlan pl, co
   }
 }
 
-template <class K>
-void ny_lds_attr(K kernel, int64_t shm) {
-  if (shm > 65536)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)shm);
-}
-
 }  // namespace
 
 extern "C" {
 
 int64_t ttk_nystroem_lds(int d, const int64_t *inner, const int64_t *ranks, const int64_t *lranks,
                          const int64_t *rranks) {
-  const int64_t b = ny_plan(d, inner, ranks, lranks, rranks, nullptr, nullptr, nullptr);
+  NyPlan p;
+  int64_t shm[3], words;
+  const int64_t b = ny_plan(d, inner, ranks, lranks, rranks, &p, shm, &words);
   return b < 0 ? -1 : b;
 }
 
@@ -314,19 +226,14 @@ int ttk_nystroem(ttk_ctx ctx, int d, const double *const *cores, const int64_t *
                  const double *const *sk_left, const int64_t *lranks, const double *const *sk_right,
                  const int64_t *rranks, double *const *out, int64_t *out_ranks) {
   ttk::CtxScope scope(ctx);
-  hipStream_t st = ttk::ctx().stream;
   NyPlan p;
   int64_t shm[3] = {0, 0, 0}, words = 0;
   const int64_t big =
       (cores && sk_left && sk_right && out && out_ranks) ? ny_plan(d, inner, ranks, lranks, rranks, &p, shm, &words) : -2;
-  if (big == -2) {
-    ttk::set_error("ttk_nystroem: bad arguments (d >= 2, every rank and extent >= 1, equal boundary ranks)");
-    return TTK_ERR_ARG;
-  }
-  if (big < 0) {
-    ttk::set_error("ttk_nystroem: a core does not fit one workgroup's LDS (ttk_nystroem_lds)");
-    return TTK_ERR_ARG;
-  }
+  if (const int e = tt_plan_status(
+          big, "ttk_nystroem: bad arguments (d >= 2, every rank and extent >= 1, equal boundary ranks)",
+          "ttk_nystroem: a core does not fit one workgroup's LDS (ttk_nystroem_lds)"))
+    return e;
   for (int k = 0; k < d; ++k) {
     if (!cores[k] || !out[k] || (k + 1 < d && !sk_left[k]) || (k > 0 && !sk_right[k])) {
       ttk::set_error("ttk_nystroem: null core %d", k);
@@ -337,34 +244,17 @@ int ttk_nystroem(ttk_ctx ctx, int d, const double *const *cores, const int64_t *
     p.skr[k] = k > 0 ? sk_right[k] : nullptr;
     p.out[k] = out[k];
   }
-  int pmax = 1;  // launch 2: one wave per Jacobi pair, up to 16 waves
-  for (int k = 1; k < d; ++k) pmax = p.q[k] > pmax ? p.q[k] : pmax;
-  const int nt2 = pmax <= 8 ? 256 : 1024;
-  void *w = nullptr;  // W_L, W_R, L, R of every bond: one stream-ordered block per call
-  TTK_HIP(hipMallocAsync(&w, (size_t)(words > 0 ? words : 2) * sizeof(double), st));
-  double *scr = static_cast<double *>(w);
-  ny_lds_attr(nystroem_sketch_kernel, shm[0]);
-  ny_lds_attr(nystroem_bond_kernel, shm[1]);
-  ny_lds_attr(nystroem_core_kernel, shm[2]);
-  hipError_t le = hipSuccess;
-  hipLaunchKernelGGL(nystroem_sketch_kernel, dim3(2), dim3(p.nt1), (size_t)shm[0], st, p, scr);
-  ttk::note_launch();
-  le = hipGetLastError();
-  if (le == hipSuccess) {
-    hipLaunchKernelGGL(nystroem_bond_kernel, dim3(d - 1), dim3(nt2), (size_t)shm[1], st, p, scr);
-    ttk::note_launch();
-    le = hipGetLastError();
-  }
-  if (le == hipSuccess) {
-    hipLaunchKernelGGL(nystroem_core_kernel, dim3(d), dim3(256), (size_t)shm[2], st, p, (const double *)scr);
-    ttk::note_launch();
-    le = hipGetLastError();
-  }
-  (void)hipFreeAsync(w, st);
-  if (le != hipSuccess) {
-    ttk::set_error("%s:%d launch: %s", __FILE__, __LINE__, hipGetErrorString(le));
-    return TTK_ERR_HIP;
-  }
+  TtScratch w(ttk::ctx().stream);  // W_L, W_R, L, R of every bond
+  TTK_HIP(w.alloc(words));
+  tt_lds_attr(nystroem_sketch_kernel, shm[0]);
+  tt_lds_attr(nystroem_bond_kernel, shm[1]);
+  tt_lds_attr(nystroem_core_kernel, shm[2]);
+  hipLaunchKernelGGL(nystroem_sketch_kernel, dim3(2), dim3(p.nt1), (size_t)shm[0], w.st, p, w.get());
+  TTK_LAUNCH_CHECK();
+  hipLaunchKernelGGL(nystroem_bond_kernel, dim3(d - 1), dim3(p.nt2), (size_t)shm[1], w.st, p, w.get());
+  TTK_LAUNCH_CHECK();
+  hipLaunchKernelGGL(nystroem_core_kernel, dim3(d), dim3(256), (size_t)shm[2], w.st, p, (const double *)w.get());
+  TTK_LAUNCH_CHECK();
   for (int k = 0; k <= d; ++k) out_ranks[k] = p.q[k];
   return TTK_OK;
 }

@@ -36,47 +36,33 @@
 
 namespace {
 
-constexpr int RT_MAXD = 32;                  // cores per train (the plan travels as a kernel argument)
-constexpr int64_t RT_LDS_MAX = 160 * 1024;   // bytes one workgroup may declare
-
 struct RtPlan {
   int d, nt;
-  int n[RT_MAXD];        // middle extents
-  int r[RT_MAXD + 1];    // train bond ranks
-  int rho[RT_MAXD + 1];  // bond ranks after the QR sweep
-  int q[RT_MAXD + 1];    // output bond ranks
-  int so[RT_MAXD];       // orthogonalised core k's offset in the scratch block (doubles), k = 1 .. d-1
+  int n[TT_MAXD];        // middle extents
+  int r[TT_MAXD + 1];    // train bond ranks
+  int rho[TT_MAXD + 1];  // bond ranks after the QR sweep
+  int q[TT_MAXD + 1];    // output bond ranks
+  int so[TT_MAXD];       // orthogonalised core k's offset in the scratch block (doubles), k = 1 .. d-1
   int oP0, oP1, oC, oG, oM, oT, oS;  // LDS regions (offsets in doubles, all even: 16-byte aligned)
-  const double *core[RT_MAXD];
-  double *out[RT_MAXD];
+  const double *core[TT_MAXD];
+  double *out[TT_MAXD];
 };
 
-__host__ __device__ inline int64_t rt_even(int64_t v) { return (v + 1) & ~(int64_t)1; }
-
 // Validates the extents, applies the rank rule and lays out LDS and scratch.  Returns the bytes of
-// dynamic LDS, -1 when the train does not fit one workgroup (or has more than RT_MAXD cores), -2 on
+// dynamic LDS, -1 when the train does not fit one workgroup (or has more than TT_MAXD cores), -2 on
 // invalid arguments.  *words: doubles of scratch for the orthogonalised cores 1 .. d-1.
 int64_t rt_plan(int d, const int64_t *inner, const int64_t *ranks, const int64_t *upper, RtPlan *p, int64_t *words) {
-  if (d < 2 || !inner || !ranks || !upper) return -2;
-  for (int k = 0; k <= d; ++k)
-    if (ranks[k] < 1) return -2;
-  for (int k = 0; k < d; ++k)
-    if (inner[k] < 1) return -2;
-  for (int k = 0; k + 1 < d; ++k)
-    if (upper[k] < 1) return -2;
-  if (ranks[0] != 1 || ranks[d] != 1) return -2;
-  if (d > RT_MAXD) return -1;
-  const int64_t cap = RT_LDS_MAX / 8;  // no single extent or product may pass the LDS capacity
-  for (int k = 0; k <= d; ++k)
-    if (ranks[k] > cap) return -1;
-  for (int k = 0; k < d; ++k)
-    if (inner[k] > cap) return -1;
+  const int chk = tt_check_extents(d, inner, {ranks});
+  bool bad = chk == -2 || !upper || ranks[0] != 1 || ranks[d] != 1;
+  for (int k = 0; !bad && k + 1 < d; ++k) bad = upper[k] < 1;
+  if (bad) return -2;
+  if (chk) return chk;
   const int64_t *n = inner, *r = ranks;
-  int64_t rho[RT_MAXD + 1], q[RT_MAXD + 1];
+  int64_t rho[TT_MAXD + 1], q[TT_MAXD + 1];
   rho[d] = 1;
   rho[0] = 1;
   for (int k = d - 1; k >= 1; --k) {
-    const int64_t m = n[k] * rho[k + 1];  // <= cap * cap: no overflow
+    const int64_t m = n[k] * rho[k + 1];  // <= TT_CAP * TT_CAP: no overflow
     rho[k] = m < r[k] ? m : r[k];
   }
   q[0] = 1;
@@ -86,62 +72,36 @@ int64_t rt_plan(int d, const int64_t *inner, const int64_t *ranks, const int64_t
     int64_t v = upper[i] < m ? upper[i] : m;
     q[i + 1] = v < rho[i + 1] ? v : rho[i + 1];
   }
-  bool over = false;
-  auto p3 = [&](int64_t a, int64_t b, int64_t c) {  // a b c, saturating at cap + 1 (factors <= cap: no overflow)
-    int64_t v = a * b;
-    v = v > cap ? cap + 1 : v * c;
-    if (v > cap) over = true, v = cap + 1;
-    return v;
-  };
-  auto up = [](int64_t &z, int64_t v) { z = v > z ? v : z; };
-  int64_t zP = 2, zC = 2, zG = 2, zM = 2, zT = 2, zS = 2, w = 0, pmax = 1;
+  TtLayout L, S;  // LDS, scratch
+  int64_t zP = 2, zC = 2, zG = 2, zM = 2, zT = 2, zS = 2, pmax = 1;
   for (int k = d - 1; k >= 1; --k) {
-    up(zP, p3(r[k], n[k], rho[k + 1]));          // carried core k; Q^T (rho_k n_k rho_{k+1}) is no larger
-    up(zP, p3(r[k - 1], n[k - 1], rho[k]));      // carried core k-1
-    up(zC, p3(r[k - 1], n[k - 1], r[k]));        // core k-1 as it lies
-    up(zT, rho[k]);                              // tau
-    const int64_t qs = p3(rho[k], n[k], rho[k + 1]);
-    up(zC, qs);                                  // orthogonalised core k, read back in phase B
-    if (over) return -1;
-    if (p) p->so[k] = (int)w;
-    w += rt_even(qs);
-    if (w > ((int64_t)1 << 30)) return -1;
+    L.up(zP, r[k], n[k], rho[k + 1]);            // carried core k; Q^T (rho_k n_k rho_{k+1}) is no larger
+    L.up(zP, r[k - 1], n[k - 1], rho[k]);        // carried core k-1
+    L.up(zC, r[k - 1], n[k - 1], r[k]);          // core k-1 as it lies
+    L.up(zT, rho[k]);                            // tau
+    const int64_t qs = L.mul(rho[k], n[k], rho[k + 1]);
+    L.up(zC, qs);                                // orthogonalised core k, read back in phase B
+    p->so[k] = S.take(qs);
   }
   for (int i = 0; i < d; ++i) {
-    up(zP, p3(q[i], n[i], rho[i + 1]));          // Z, and the Jacobi's rows (Z or Z^T)
-    if (over) return -1;
+    L.up(zP, q[i], n[i], rho[i + 1]);            // Z, and the Jacobi's rows (Z or Z^T)
     if (i + 1 == d) break;
     const int64_t m = q[i] * n[i], pp = m < rho[i + 1] ? m : rho[i + 1];
-    up(zG, p3(pp, pp, 1));
-    up(zS, pp);
-    up(pmax, pp);
-    up(zM, p3(q[i + 1], rho[i + 1], 1));
-    if (over) return -1;
+    L.up(zG, pp, pp);
+    L.up(zS, pp);
+    L.up(pmax, pp);
+    L.up(zM, q[i + 1], rho[i + 1]);
   }
-  const int64_t total =
-      2 * rt_even(zP) + rt_even(zC) + rt_even(zG) + rt_even(zM) + rt_even(zT) + 2 * rt_even(zS) + NY_FLAGS;
-  if (total * 8 > RT_LDS_MAX) return -1;
-  if (words) *words = w;
-  if (p) {
-    p->d = d;
-    for (int k = 0; k < d; ++k) p->n[k] = (int)n[k];
-    for (int k = 0; k <= d; ++k) {
-      p->r[k] = (int)r[k];
-      p->rho[k] = (int)rho[k];
-      p->q[k] = (int)q[k];
-    }
-    int64_t o = 0;
-    p->oP0 = (int)o, o += rt_even(zP);
-    p->oP1 = (int)o, o += rt_even(zP);
-    p->oC = (int)o, o += rt_even(zC);
-    p->oG = (int)o, o += rt_even(zG);
-    p->oM = (int)o, o += rt_even(zM);
-    p->oT = (int)o, o += rt_even(zT);
-    p->oS = (int)o;  // sv, perm, flags
-    // small trains: fewer waves at each barrier; one wave per Jacobi pair, up to 16 waves
-    p->nt = ((zP > zC ? zP : zC) <= 2048 && pmax <= 8) ? 256 : 1024;
-  }
-  return total * 8;
+  p->oP0 = L.take(zP), p->oP1 = L.take(zP), p->oC = L.take(zC), p->oG = L.take(zG), p->oM = L.take(zM);
+  p->oT = L.take(zT), p->oS = L.take(zS);  // sv, then perm and the flags
+  L.take(zS), L.take(NY_FLAGS);
+  if (L.over || L.words * 8 > TT_LDS_MAX) return -1;
+  *words = S.words;
+  p->d = d;
+  p->nt = tt_threads(zP > zC ? zP : zC, pmax);
+  for (int k = 0; k < d; ++k) p->n[k] = (int)n[k];
+  for (int k = 0; k <= d; ++k) p->r[k] = (int)r[k], p->rho[k] = (int)rho[k], p->q[k] = (int)q[k];
+  return L.words * 8;
 }
 
 __global__ __launch_bounds__(1024) void retract_kernel(const RtPlan p, double *scr) {
@@ -149,7 +109,6 @@ __global__ __launch_bounds__(1024) void retract_kernel(const RtPlan p, double *s
   double *P[2] = {rt_lds + p.oP0, rt_lds + p.oP1};
   double *C = rt_lds + p.oC, *G = rt_lds + p.oG, *Mq = rt_lds + p.oM, *tau = rt_lds + p.oT, *sv = rt_lds + p.oS;
   const int d = p.d;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
   int cur = 0;
   // ---- phase A: right to left; P[cur] holds the carried core k as (r_k, n_k rho_{k+1})
   ro_load(P[0], p.core[d - 1], p.r[d - 1] * p.n[d - 1]);
@@ -178,37 +137,12 @@ __global__ __launch_bounds__(1024) void retract_kernel(const RtPlan p, double *s
     const int m = p.q[i] * p.n[i], R = p.rho[i + 1], qn = p.q[i + 1], rest = p.n[i + 1] * p.rho[i + 2];
     const bool rowsz = m <= R;  // rotate the rows of Z, else those of Z^T
     const int pp = rowsz ? m : R, n = rowsz ? R : m;
-    int *perm = reinterpret_cast<int *>(sv + rt_even(pp));
-    int *flag = reinterpret_cast<int *>(sv + 2 * rt_even(pp));
     ro_load(C, scr + p.so[i + 1], R * rest);
     for (int e = threadIdx.x; e < m * R; e += blockDim.x) {
       const int a = e / R, c = e - a * R;
       A[rowsz ? e : c * m + a] = Z[e];
     }
-    for (int e = threadIdx.x; e < pp * pp; e += blockDim.x) G[e] = (e / pp == e % pp) ? 1.0 : 0.0;
-    for (int e = threadIdx.x; e < NY_SWEEPS; e += blockDim.x) flag[e] = 0;
-    for (int e = threadIdx.x; e < pp; e += blockDim.x) perm[e] = e;  // stays a valid index whatever the sort meets
-    __syncthreads();
-    const double tol = NY_EPS * (n > 16 ? (double)n : 16.0), tol2 = tol * tol;
-    const int me = (pp + 1) & ~1;
-    for (int sweep = 0; sweep < NY_SWEEPS && pp > 1; ++sweep) {
-      for (int round = 0; round < me - 1; ++round) ny_jacobi_round(A, G, pp, n, me, round, tol2, flag + sweep);
-      if (flag[sweep] == 0) break;  // written before the round's barrier: every thread reads the same value
-    }
-    // sigma_j = ||row j||, sorted descending (ties by index): perm[position] = row
-    for (int j = wid; j < pp; j += nw) {
-      double part = 0.0;
-      for (int c = lane; c < n; c += 64) part = fma(A[j * n + c], A[j * n + c], part);
-      const double nrm = sqrt(ttk::wave_sum(part));
-      if (lane == 0) sv[j] = nrm;
-    }
-    __syncthreads();
-    for (int j = threadIdx.x; j < pp; j += blockDim.x) {
-      int pos = 0;
-      for (int t = 0; t < pp; ++t) pos += (sv[t] > sv[j] || (sv[t] == sv[j] && t < j)) ? 1 : 0;
-      perm[pos < pp ? pos : pp - 1] = j;  // a NaN compares false everywhere: stay in bounds
-    }
-    __syncthreads();
+    const int *perm = tt_jacobi_svd(A, G, sv, pp, n);
     // rows of Z:   G = U^T, A = diag(S) V^T:  out_i = G^T[:, top],        M = A[top]
     // rows of Z^T: G = V^T, A = diag(S) U^T:  out_i = (A / S)^T[:, top],  M = diag(S) G[top]
     double *oi = p.out[i];
@@ -240,25 +174,22 @@ __global__ __launch_bounds__(1024) void retract_kernel(const RtPlan p, double *s
 extern "C" {
 
 int64_t ttk_retract_lds(int d, const int64_t *inner, const int64_t *ranks, const int64_t *upper) {
-  const int64_t b = rt_plan(d, inner, ranks, upper, nullptr, nullptr);
+  RtPlan p;
+  int64_t words;
+  const int64_t b = rt_plan(d, inner, ranks, upper, &p, &words);
   return b < 0 ? -1 : b;
 }
 
 int ttk_retract(ttk_ctx ctx, int d, const double *const *cores, const int64_t *inner, const int64_t *ranks,
                 const int64_t *upper, double *const *out, int64_t *out_ranks) {
   ttk::CtxScope scope(ctx);
-  hipStream_t st = ttk::ctx().stream;
   RtPlan p;
   int64_t words = 0;
   const int64_t shm = (cores && out && out_ranks) ? rt_plan(d, inner, ranks, upper, &p, &words) : -2;
-  if (shm == -2) {
-    ttk::set_error("ttk_retract: bad arguments (d >= 2, every rank, extent and upper >= 1, boundary ranks 1)");
-    return TTK_ERR_ARG;
-  }
-  if (shm < 0) {
-    ttk::set_error("ttk_retract: the train does not fit one workgroup's LDS (ttk_retract_lds)");
-    return TTK_ERR_ARG;
-  }
+  if (const int e = tt_plan_status(
+          shm, "ttk_retract: bad arguments (d >= 2, every rank, extent and upper >= 1, boundary ranks 1)",
+          "ttk_retract: the train does not fit one workgroup's LDS (ttk_retract_lds)"))
+    return e;
   for (int k = 0; k < d; ++k) {
     if (!cores[k] || !out[k]) {
       ttk::set_error("ttk_retract: null core %d", k);
@@ -267,19 +198,11 @@ int ttk_retract(ttk_ctx ctx, int d, const double *const *cores, const int64_t *i
     p.core[k] = cores[k];
     p.out[k] = out[k];
   }
-  void *w = nullptr;  // the orthogonalised cores 1 .. d-1: one stream-ordered block per call
-  TTK_HIP(hipMallocAsync(&w, (size_t)(words > 0 ? words : 2) * sizeof(double), st));
-  if (shm > 65536)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(retract_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)shm);
-  hipLaunchKernelGGL(retract_kernel, dim3(1), dim3(p.nt), (size_t)shm, st, p, static_cast<double *>(w));
-  const hipError_t le = hipGetLastError();
-  (void)hipFreeAsync(w, st);
-  ttk::note_launch();
-  if (le != hipSuccess) {
-    ttk::set_error("%s:%d launch: %s", __FILE__, __LINE__, hipGetErrorString(le));
-    return TTK_ERR_HIP;
-  }
+  TtScratch w(ttk::ctx().stream);  // the orthogonalised cores 1 .. d-1
+  TTK_HIP(w.alloc(words));
+  tt_lds_attr(retract_kernel, shm);
+  hipLaunchKernelGGL(retract_kernel, dim3(1), dim3(p.nt), (size_t)shm, w.st, p, w.get());
+  TTK_LAUNCH_CHECK();
   for (int k = 0; k <= d; ++k) out_ranks[k] = p.q[k];
   return TTK_OK;
 }

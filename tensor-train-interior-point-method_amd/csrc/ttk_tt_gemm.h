@@ -1,10 +1,17 @@
-// Products, loads, the Householder QR and the one-sided Jacobi round shared by the one-workgroup TT
-// kernels (ttk_randorth.hip, ttk_nystroem.hip, ttk_retract.hip).
-// The summation order is part of their contract: one ascending-k fma chain per output element.
+// What the one-workgroup TT rounding kernels (ttk_randorth.hip, ttk_nystroem.hip, ttk_retract.hip) share:
+//   device   products and loads, the right-to-left sketch step, the Householder QR, the one-sided
+//            Jacobi round and the Jacobi SVD built on it;
+//   host     the planners' constants, extents check, saturating sizes and region allocator, and the
+//            entry points' scratch block, LDS attribute and plan-status mapping.
+// Each .hip file keeps its plan struct, its region sizes and its kernels' phase structure.
+// The summation order is part of the contract: one ascending-k fma chain per output element.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <initializer_list>
+
 #include "ttk_common.h"
+#include "ttk_internal.h"
 
 // C(i, j) = sum_k a(i, k) b(k, j), k ascending in one fma chain from 0; element e = i N + j goes to
 // thread e mod blockDim.x.
@@ -20,6 +27,35 @@ __device__ __forceinline__ void ro_gemm(int M, int N, int K, FA a, FB b, FC stor
 
 __device__ __forceinline__ void ro_load(double *dst, const double *src, int n) {
   for (int e = threadIdx.x; e < n; e += blockDim.x) dst[e] = src[e];
+}
+
+__host__ __device__ inline int64_t tt_even(int64_t v) { return (v + 1) & ~(int64_t)1; }  // 16-byte aligned regions
+
+// One step of the right-to-left sketch chain, W_k (rk x sk) = unfold(A_k W_{k+1}) unfold(B_k)^T, with
+// A_k (rk, n, r1) at `core`, B_k (sk, n, s1) at `sketch` and W_{k+1} (r1 x s1) in W on entry: loads
+// both cores into C and Z, forms T = A_k W_{k+1} (rk n x s1) in Y, then W_k into W and into wk.
+// direct: the last core meets its sketch core as it lies (T = A_k, r1 == s1; W and Y are not read).
+// Ends with a barrier.
+__device__ __forceinline__ void tt_sketch_step(const double *core, const double *sketch, int rk, int n, int r1, int sk,
+                                               int s1, bool direct, double *C, double *Z, double *Y, double *W,
+                                               double *wk) {
+  ro_load(C, core, rk * n * r1);
+  ro_load(Z, sketch, sk * n * s1);
+  __syncthreads();
+  const double *T = C;
+  if (!direct) {
+    ro_gemm(rk * n, s1, r1, [&](int i, int c) { return C[i * r1 + c]; }, [&](int c, int j) { return W[c * s1 + j]; },
+            [&](int i, int j, double v) { Y[i * s1 + j] = v; });
+    __syncthreads();
+    T = Y;
+  }
+  const int K = n * s1;
+  ro_gemm(rk, sk, K, [&](int i, int c) { return T[i * K + c]; }, [&](int c, int j) { return Z[j * K + c]; },
+          [&](int i, int j, double v) {
+            W[i * sk + j] = v;
+            wk[i * sk + j] = v;
+          });
+  __syncthreads();
 }
 
 namespace {
@@ -144,6 +180,124 @@ __device__ void ny_jacobi_round(double *A, double *G, int p, int n, int m, int r
     if (lane == 0) *flag = 1;
   }
   __syncthreads();
+}
+
+// One-sided Jacobi SVD of the rows of A (p x n, in LDS; the caller gives whichever of its matrix and
+// the transpose has fewer rows): on return A = diag(S) W^T with the rotations accumulated in G
+// (p x p, G A_in = A_out), sv[j] = ||row j|| and perm[position] = row, descending (ties by index).
+// sv holds 2 tt_even(p) doubles and NY_FLAGS more: the values, perm (returned) and the sweep flags.
+// Contract: call it once A is written, with no barrier in between.  It sets G, perm and the flags
+// (none of them A), waits at ONE barrier, which also publishes A, then runs at most NY_SWEEPS sweeps,
+// the row norms and the sort.  Ends with a barrier.
+__device__ int *tt_jacobi_svd(double *A, double *G, double *sv, int p, int n) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  int *perm = reinterpret_cast<int *>(sv + tt_even(p));
+  int *flag = reinterpret_cast<int *>(sv + 2 * tt_even(p));
+  for (int e = threadIdx.x; e < p * p; e += blockDim.x) G[e] = (e / p == e % p) ? 1.0 : 0.0;
+  for (int e = threadIdx.x; e < NY_SWEEPS; e += blockDim.x) flag[e] = 0;
+  for (int e = threadIdx.x; e < p; e += blockDim.x) perm[e] = e;  // stays a valid index whatever the sort meets
+  __syncthreads();
+  const double tol = NY_EPS * (n > 16 ? (double)n : 16.0), tol2 = tol * tol;
+  const int m = (p + 1) & ~1;
+  for (int sweep = 0; sweep < NY_SWEEPS && p > 1; ++sweep) {
+    for (int round = 0; round < m - 1; ++round) ny_jacobi_round(A, G, p, n, m, round, tol2, flag + sweep);
+    if (flag[sweep] == 0) break;  // written before the round's barrier: every thread reads the same value
+  }
+  for (int j = wid; j < p; j += nw) {
+    double part = 0.0;
+    for (int c = lane; c < n; c += 64) part = fma(A[j * n + c], A[j * n + c], part);
+    const double nrm = sqrt(ttk::wave_sum(part));
+    if (lane == 0) sv[j] = nrm;
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < p; j += blockDim.x) {
+    int pos = 0;
+    for (int i = 0; i < p; ++i) pos += (sv[i] > sv[j] || (sv[i] == sv[j] && i < j)) ? 1 : 0;
+    perm[pos < p ? pos : p - 1] = j;  // a NaN compares false everywhere: stay in bounds
+  }
+  __syncthreads();
+  return perm;
+}
+
+// ---- host: planning
+constexpr int TT_MAXD = 32;                 // cores per train (the plan travels as a kernel argument)
+constexpr int64_t TT_LDS_MAX = 160 * 1024;  // bytes one workgroup may declare
+constexpr int64_t TT_CAP = TT_LDS_MAX / 8;  // doubles: no single extent or product may pass the LDS capacity
+
+// The planners' common checks on d middle extents and rank arrays of d + 1 entries: -2 unless d >= 2,
+// no array is null and every entry is >= 1; then -1 for more than TT_MAXD cores or an entry above
+// TT_CAP; else 0.  A planner adds its boundary rule to the -2 case before it passes a -1 on.
+inline int tt_check_extents(int d, const int64_t *inner, std::initializer_list<const int64_t *> ranks) {
+  if (d < 2 || !inner) return -2;
+  for (const int64_t *r : ranks)
+    if (!r) return -2;
+  bool big = d > TT_MAXD;
+  for (int k = 0; k <= d; ++k)
+    for (const int64_t *r : ranks) {
+      if (r[k] < 1) return -2;
+      big |= r[k] > TT_CAP;
+    }
+  for (int k = 0; k < d; ++k) {
+    if (inner[k] < 1) return -2;
+    big |= inner[k] > TT_CAP;
+  }
+  return big ? -1 : 0;
+}
+
+// Sizes and offsets in doubles.  up: z = max(z, a b c) with the product saturating at TT_CAP + 1
+// (factors <= TT_CAP: no overflow), which `over` remembers.  take: the next region of a block (LDS, or
+// the call's scratch), regions back to back and rounded up to even; a plan has at most 4 TT_MAXD of
+// them, none above TT_CAP + 2, so an offset fits an int.
+struct TtLayout {
+  bool over = false;
+  int64_t words = 0;
+  int64_t mul(int64_t a, int64_t b = 1, int64_t c = 1) {
+    int64_t v = a * b;
+    v = v > TT_CAP ? TT_CAP + 1 : v * c;
+    if (v > TT_CAP) over = true, v = TT_CAP + 1;
+    return v;
+  }
+  void up(int64_t &z, int64_t a, int64_t b = 1, int64_t c = 1) {
+    const int64_t v = mul(a, b, c);
+    z = v > z ? v : z;
+  }
+  int take(int64_t z) {
+    const int at = (int)words;
+    words += tt_even(z);
+    return at;
+  }
+};
+
+// small trains: fewer waves at each barrier; a Jacobi takes one wave per pair, up to 16 waves
+inline int tt_threads(int64_t work, int64_t jacobi_rows) { return (work <= 2048 && jacobi_rows <= 8) ? 256 : 1024; }
+
+// ---- host: the entry points
+// the call's stream-ordered scratch block: allocated on the stream, freed on it when the call returns
+struct TtScratch {
+  hipStream_t st;
+  void *p = nullptr;
+  explicit TtScratch(hipStream_t s) : st(s) {}
+  TtScratch(const TtScratch &) = delete;
+  TtScratch &operator=(const TtScratch &) = delete;
+  ~TtScratch() {
+    if (p) (void)hipFreeAsync(p, st);
+  }
+  hipError_t alloc(int64_t words) { return hipMallocAsync(&p, (size_t)(words > 0 ? words : 2) * sizeof(double), st); }
+  double *get() const { return static_cast<double *>(p); }
+};
+
+template <class K>
+void tt_lds_attr(K kernel, int64_t shm) {
+  if (shm > 65536)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)shm);
+}
+
+// a planner's result as the entry point's status: TTK_OK, or TTK_ERR_ARG with the message set
+inline int tt_plan_status(int64_t shm, const char *bad_arguments, const char *does_not_fit) {
+  if (shm >= 0) return TTK_OK;
+  ttk::set_error("%s", shm == -2 ? bad_arguments : does_not_fit);
+  return TTK_ERR_ARG;
 }
 
 }  // namespace

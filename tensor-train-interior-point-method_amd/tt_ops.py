@@ -408,12 +408,51 @@ def retraction_ranks(inner, ranks, upper):
 NATIVE_RETRACT = os.environ.get("TTIPM_NATIVE_RETRACT", "0") == "1"
 
 
-def _retract_args(tt, upper):
-    d = len(tt)
+def _inner(c):
+    return int(np.prod(c.shape[1:-1])) if c.dim() > 2 else 1
+
+
+def _tt_extents(*trains):
+    """ctypes int64 arrays for the native rounding calls: the middle extents of the first train (d entries),
+    then one bond-rank array per train (d + 1 entries, boundaries included)."""
+    d = len(trains[0])
     I64 = ctypes.c_int64
-    inner = (I64 * d)(*[int(np.prod(c.shape[1:-1])) for c in tt])
-    ranks = (I64 * (d + 1))(*([tt[0].shape[0]] + [c.shape[-1] for c in tt]))
-    return inner, ranks, (I64 * max(d - 1, 1))(*[int(u) for u in upper])
+    inner = (I64 * d)(*[_inner(c) for c in trains[0]])
+    return (inner,) + tuple((I64 * (d + 1))(*([t[0].shape[0]] + [c.shape[-1] for c in t])) for t in trains)
+
+
+def _packed_out(tt, rk, inner):
+    """One fresh buffer for the output cores of ranks `rk`: its flat slices, one per core (what a native
+    call writes), and their views (rk[k], *middle extents of tt[k], rk[k+1])."""
+    sizes = [rk[k] * inner[k] * rk[k + 1] for k in range(len(tt))]
+    offs = np.concatenate(([0], np.cumsum([(s + 1) & ~1 for s in sizes])))  # 16-byte aligned cores
+    buf = D.empty(int(offs[-1]))
+    outs = [buf[int(o):int(o) + s] for o, s in zip(offs, sizes)]
+    return outs, [o.view(rk[k], *tt[k].shape[1:-1], rk[k + 1]) for k, o in enumerate(outs)]
+
+
+def _native_rounding(name, tt, rk, inner, args):
+    """Calls `ttk_<name>(ctx, d, *args, out, out_ranks)` into a `_packed_out` buffer and returns the output
+    cores.  In `args` a list of tensors stands for the array of their (contiguous) device pointers.  No
+    host read: the ranks `rk` are host arithmetic, and the library's own rule must agree with them."""
+    d = len(tt)
+    P = ctypes.c_void_p * d
+    outs, views = _packed_out(tt, rk, inner)
+    keep, call = [], []  # keep: the contiguous inputs stay alive until the call is enqueued
+    for a in args:
+        if isinstance(a, list):
+            keep.append([D.contig(c) for c in a])
+            a = P(*[c.data_ptr() for c in keep[-1]])
+        call.append(a)
+    got = (ctypes.c_int64 * (d + 1))()
+    D._stream()
+    D.check(getattr(D.lib, "ttk_" + name)(D.ctx(), d, *call, P(*[o.data_ptr() for o in outs]), got), name)
+    assert list(got) == rk, (list(got), rk)
+    return views
+
+
+def _retract_args(tt, upper):
+    return _tt_extents(tt) + ((ctypes.c_int64 * max(len(tt) - 1, 1))(*[int(u) for u in upper]),)
 
 
 def retract_lds(tt, upper):
@@ -424,25 +463,12 @@ def retract_lds(tt, upper):
     return int(D.lib.ttk_retract_lds(len(tt), *_retract_args(tt, upper)))
 
 
-def _retract_native(tt, upper):
+def _retract_native(tt, args):
     """`ttk_retract`: the QR sweep and the Jacobi-SVD sweep in one launch of one workgroup, into one
     fresh buffer (the output cores are views of it).  No host read: the ranks come from
-    `retraction_ranks`."""
-    d = len(tt)
-    inner, ranks, ub = _retract_args(tt, upper)
-    rk = retraction_ranks(inner, ranks, ub)
-    cs = [D.contig(c) for c in tt]
-    sizes = [rk[k] * inner[k] * rk[k + 1] for k in range(d)]
-    offs = np.concatenate(([0], np.cumsum([(s + 1) & ~1 for s in sizes])))  # 16-byte aligned cores
-    buf = D.empty(int(offs[-1]))
-    outs = [buf[int(offs[k]):int(offs[k]) + sizes[k]] for k in range(d)]
-    P = ctypes.c_void_p
-    got = (ctypes.c_int64 * (d + 1))()
-    D._stream()
-    D.check(D.lib.ttk_retract(D.ctx(), d, (P * d)(*[c.data_ptr() for c in cs]), inner, ranks, ub,
-                              (P * d)(*[o.data_ptr() for o in outs]), got), "retract")
-    assert list(got) == rk, (list(got), rk)
-    return [o.view(rk[k], *tt[k].shape[1:-1], rk[k + 1]) for k, o in enumerate(outs)]
+    `retraction_ranks`.  `args`: `_retract_args`."""
+    inner, ranks, ub = args
+    return _native_rounding("retract", tt, retraction_ranks(inner, ranks, ub), inner, (list(tt), inner, ranks, ub))
 
 
 def tt_rank_retraction(tt, upper_ranks):
@@ -451,10 +477,11 @@ def tt_rank_retraction(tt, upper_ranks):
     (`retract_lds`): one launch without a host read (`ttk_retract`), the same tensor in another gauge;
     the caller's tensors are never written and the list is rebound in place.  Off by default: the
     whole-solve goldens are pinned to the composed path's arithmetic."""
-    if (NATIVE_RETRACT and D.DEV.type == "cuda" and len(tt) > 1 and len(upper_ranks) == len(tt) - 1
-            and retract_lds(tt, upper_ranks) >= 0):
-        tt[:] = _retract_native(tt, upper_ranks)
-        return tt
+    if NATIVE_RETRACT and D.DEV.type == "cuda" and len(tt) > 1 and len(upper_ranks) == len(tt) - 1:
+        args = _retract_args(tt, upper_ranks)  # built once for the fit check and the call
+        if D.lib.ttk_retract_lds(len(tt), *args) >= 0:
+            tt[:] = _retract_native(tt, args)
+            return tt
     tt = tt_rl_orthogonalise_py(tt)
     rank = 1
     for idx, up in enumerate(upper_ranks):
@@ -514,10 +541,6 @@ def randorth_ranks(r0, inner, sketch_ranks):
 NATIVE_RANDORTH = os.environ.get("TTIPM_NATIVE_RANDORTH", "1") == "1"
 
 
-def _inner(c):
-    return int(np.prod(c.shape[1:-1])) if c.dim() > 2 else 1
-
-
 def _randorth_composed(tt, gs):
     """The sweep from D.einsum / D.matmul / D.qr (3 launches and a QR per bond); also what a train too
     large for `ttk_rand_orth` takes."""
@@ -538,46 +561,20 @@ def _randorth_composed(tt, gs):
     return out
 
 
-def _randorth_args(tt, gs):
-    d = len(tt)
-    I64 = ctypes.c_int64
-    inner = (I64 * d)(*[_inner(c) for c in tt])
-    ranks = (I64 * (d + 1))(*([tt[0].shape[0]] + [c.shape[-1] for c in tt]))
-    sranks = (I64 * (d + 1))(*([gs[0].shape[0]] + [c.shape[-1] for c in gs]))
-    return inner, ranks, sranks
-
-
 def randorth_lds(tt, gs):
     """Bytes of LDS `ttk_rand_orth` needs for this train and sketch, -1 if they do not fit one
     workgroup (the composed path then runs)."""
-    return int(D.lib.ttk_rand_orth_lds(len(tt), *_randorth_args(tt, gs)))
+    return int(D.lib.ttk_rand_orth_lds(len(tt), *_tt_extents(tt, gs)))
 
 
-def _randorth_native(tt, gs):
+def _randorth_native(tt, gs, args):
     """`ttk_rand_orth`: the whole sweep in one launch of one workgroup, into one fresh buffer (the
-    output cores are views of it).  No host read: the ranks come from `randorth_ranks`."""
+    output cores are views of it).  No host read: the ranks come from `randorth_ranks`.  `args`:
+    `_tt_extents(tt, gs)`."""
     d = len(tt)
-    inner, ranks, sranks = _randorth_args(tt, gs)
+    inner, ranks, sranks = args
     rk = randorth_ranks(ranks[0], inner[:d - 1], sranks[1:d]) + [ranks[d]]
-    cs = [D.contig(c) for c in tt]
-    ss = [D.contig(c) for c in gs]
-    sizes = [rk[k] * inner[k] * rk[k + 1] for k in range(d)]
-    offs = np.concatenate(([0], np.cumsum([(s + 1) & ~1 for s in sizes])))  # 16-byte aligned cores
-    buf = D.empty(int(offs[-1]))
-    outs = [buf[int(offs[k]):int(offs[k]) + sizes[k]] for k in range(d)]
-    P = ctypes.c_void_p
-    got = (ctypes.c_int64 * (d + 1))()
-    D._stream()
-    D.check(D.lib.ttk_rand_orth(D.ctx(), d, (P * d)(*[c.data_ptr() for c in cs]), inner, ranks,
-                                (P * d)(*[c.data_ptr() for c in ss]), sranks,
-                                (P * d)(*[o.data_ptr() for o in outs]), got), "rand_orth")
-    assert list(got) == rk, (list(got), rk)
-    return [o.view(rk[k], *tt[k].shape[1:-1], rk[k + 1]) for k, o in enumerate(outs)]
-
-
-def _use_native_randorth(tt, gs):
-    return (NATIVE_RANDORTH and D.DEV.type == "cuda" and hasattr(D.lib, "ttk_rand_orth")
-            and randorth_lds(tt, gs) >= 0)
+    return _native_rounding("rand_orth", tt, rk, inner, (list(tt), inner, ranks, list(gs), sranks))
 
 
 def _tt_lr_random_orthogonalise(tt, gs):
@@ -591,8 +588,12 @@ def _tt_lr_random_orthogonalise(tt, gs):
     else composed from einsum / QR launches (TTIPM_NATIVE_RANDORTH=0: always composed)."""
     if len(tt) < 2:
         return tt
-    out = _randorth_native(tt, gs) if _use_native_randorth(tt, gs) else _randorth_composed(tt, gs)
-    tt[:] = out
+    out = None
+    if NATIVE_RANDORTH and D.DEV.type == "cuda" and hasattr(D.lib, "ttk_rand_orth"):
+        args = _tt_extents(tt, gs)  # built once for the fit check and the call
+        if D.lib.ttk_rand_orth_lds(len(tt), *args) >= 0:
+            out = _randorth_native(tt, gs, args)
+    tt[:] = out if out is not None else _randorth_composed(tt, gs)
     return tt
 
 
@@ -675,38 +676,18 @@ def _nystroem_composed(tt, g1, g2):
     return out
 
 
-def _nystroem_args(tt, g1, g2):
-    d = len(tt)
-    I64 = ctypes.c_int64
-    inner = (I64 * d)(*[_inner(c) for c in tt])
-    return (inner,) + tuple((I64 * (d + 1))(*([t[0].shape[0]] + [c.shape[-1] for c in t])) for t in (tt, g1, g2))
-
-
 def nystroem_lds(tt, g1, g2):
     """The largest dynamic-LDS request (bytes) of `ttk_nystroem`'s launches for this train and these
     sketches, -1 if some core does not fit one workgroup (the composed path then runs)."""
-    return int(D.lib.ttk_nystroem_lds(len(tt), *_nystroem_args(tt, g1, g2)))
+    return int(D.lib.ttk_nystroem_lds(len(tt), *_tt_extents(tt, g1, g2)))
 
 
 def _nystroem_native(tt, g1, g2, args):
     """`ttk_nystroem`: three launches of independent workgroups into one fresh buffer (the output cores
-    are views of it).  No host read: the ranks come from `nystroem_ranks`.  `args`: `_nystroem_args`."""
-    d = len(tt)
+    are views of it).  No host read: the ranks come from `nystroem_ranks`.  `args`: `_tt_extents(tt, g1, g2)`."""
     inner, ranks, lranks, rranks = args
-    rk = nystroem_ranks(ranks, lranks, rranks)
-    cs, s1, s2 = ([D.contig(c) for c in t] for t in (tt, g1, g2))
-    sizes = [rk[k] * inner[k] * rk[k + 1] for k in range(d)]
-    offs = np.concatenate(([0], np.cumsum([(s + 1) & ~1 for s in sizes])))  # 16-byte aligned cores
-    buf = D.empty(int(offs[-1]))
-    outs = [buf[int(offs[k]):int(offs[k]) + sizes[k]] for k in range(d)]
-    P = ctypes.c_void_p
-    ptrs = lambda ts: (P * d)(*[t.data_ptr() for t in ts])  # noqa: E731
-    got = (ctypes.c_int64 * (d + 1))()
-    D._stream()
-    D.check(D.lib.ttk_nystroem(D.ctx(), d, ptrs(cs), inner, ranks, ptrs(s1), lranks, ptrs(s2), rranks, ptrs(outs), got),
-            "nystroem")
-    assert list(got) == rk, (list(got), rk)
-    return [o.view(rk[k], *tt[k].shape[1:-1], rk[k + 1]) for k, o in enumerate(outs)]
+    return _native_rounding("nystroem", tt, nystroem_ranks(ranks, lranks, rranks), inner,
+                            (list(tt), inner, ranks, list(g1), lranks, list(g2), rranks))
 
 
 def _tt_generalised_nystroem(tt, g1, g2):
@@ -722,7 +703,7 @@ def _tt_generalised_nystroem(tt, g1, g2):
         return tt
     out = None
     if NATIVE_NYSTROEM and D.DEV.type == "cuda" and hasattr(D.lib, "ttk_nystroem"):
-        args = _nystroem_args(tt, g1, g2)  # built once for the fit check and the call
+        args = _tt_extents(tt, g1, g2)  # built once for the fit check and the call
         if D.lib.ttk_nystroem_lds(len(tt), *args) >= 0:
             out = _nystroem_native(tt, g1, g2, args)
     tt[:] = out if out is not None else _nystroem_composed(tt, g1, g2)

@@ -11,18 +11,17 @@ part in value checks only if 50 x noise <= 1e-11 (50: the parity policy's multip
 That condition is asserted here on import, so a regenerated fixture cannot bring in an ill-posed
 case.  Case z (P singular at the first bond, cond ~ 1e17) is in the fixture for shapes only: the
 reference's 1/sqrt(~0) output is rounding noise.  Output ranks are host arithmetic: exact."""
-import os
-
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-G = np.load(os.path.join(HERE, "golden", "nystroem.npz"))
+from tests.tt_cases import J_SHAPES, close, dense, load  # noqa: F401  (re-exported)
+
+_F = load("nystroem.npz")
+G, _tt, train, check_rng_state = _F.G, _F._tt, _F.train, _F.check_rng_state
 
 VALUE = ("a", "b", "c", "d", "e", "f", "g", "h", "k", "j")   # every case with d >= 2 but z
 FIT = ("a", "b", "c", "d", "e", "f", "g", "h", "k")          # value cases whose cores fit one workgroup's LDS
 PUBLIC = ("c", "g")
 REPRODUCE = ("a", "e", "k")                                   # every target >= the tensor's own TT rank
-J_SHAPES = [(1, 4, 4, 96), (96, 4, 4, 96), (96, 4, 4, 1)]
 RTOL = 1e-11
 NOISE_MULTIPLE = 50
 
@@ -33,28 +32,25 @@ for _c in PUBLIC:
 assert float(G["z/cond"]) > 1e15  # z stays the singular case it is meant to be
 
 
-def _tt(key):
-    return [G[f"{key}/{i}"].copy() for i in range(int(G[key + "/n"]))]
-
-
-_INPUTS = {}
 _DENSE = {}
-
-
-def train(cid):
-    """The case's input train (host arrays; a fresh copy per call)."""
-    if cid not in _INPUTS:
-        if cid == "j":  # too large to store: regenerated from the recorded seed (legacy stream: frozen)
-            rs = np.random.RandomState(int(G["j/seed"]))
-            _INPUTS[cid] = [rs.randn(*s) for s in J_SHAPES]
-        else:
-            _INPUTS[cid] = _tt(f"{cid}/in")
-    return [c.copy() for c in _INPUTS[cid]]
 
 
 def sketches(cid):
     """(left sketch, right sketch): the reference's tt_gaussian_1 and tt_gaussian_2"""
     return _tt(f"{cid}/sk1"), _tt(f"{cid}/sk2")
+
+
+TRANSPOSED_SEED = 27   # cond(P) 5 at both bonds; 50 x noise 1.1e-13 on the CPU
+
+
+def transposed_case():
+    """(train, left sketch, right sketch), seeded: d = 3, middle extents (2, 2), bond ranks 6, left sketch
+    ranks (1, 5, 5, 1) above the right ones (1, 3, 3, 1), so the bond SVD rotates the rows of P^T, which
+    no fixture case does.  A true truncation (6 -> 3): tests/test_host_nystroem.py asserts that this
+    seed is as well posed as the fixture's value cases."""
+    rs = np.random.RandomState(TRANSPOSED_SEED)
+    return tuple([rs.randn(a, 2, 2, b) for a, b in zip(rk[:-1], rk[1:])]
+                 for rk in ((1, 6, 6, 1), (1, 5, 5, 1), (1, 3, 3, 1)))
 
 
 def targets(cid):
@@ -66,13 +62,6 @@ def contractions(cid, which):
     return [G[f"{cid}/{which}/{k}"] for k in range(len(targets(cid)))]
 
 
-def dense(tt):
-    t = tt[0]
-    for c in tt[1:]:
-        t = np.tensordot(t, c, axes=(-1, 0))
-    return np.sum(t, axis=(0, -1))
-
-
 def reference_dense(cid, which="out"):
     """The tensor the reference's output represents (computed once per case, shared, read only)."""
     key = f"{cid}/{which}"
@@ -80,12 +69,6 @@ def reference_dense(cid, which="out"):
         _DENSE[key] = dense(_tt(key))
         _DENSE[key].setflags(write=False)
     return _DENSE[key]
-
-
-def close(a, b, rtol):
-    scale = max(np.max(np.abs(b)), 1e-300)
-    err = np.max(np.abs(np.asarray(a) - b)) / scale
-    assert err <= rtol, err
 
 
 def check_shapes(cid, res_host, which=""):
@@ -101,11 +84,3 @@ def check_result(cid, res_host, which=""):
     """exact ranks, bond consistency, dense tensor to 1e-11 (which = "pub_": the public call)"""
     check_shapes(cid, res_host, which)
     close(dense(res_host), reference_dense(cid, which + "out"), RTOL)
-
-
-def check_rng_state(cid):
-    """NumPy's global MT19937 state equals the one the reference's public call left"""
-    st = np.random.get_state()
-    assert np.array_equal(st[1], G[f"{cid}/pub_key"])
-    assert st[2] == int(G[f"{cid}/pub_pos"]) and st[3] == int(G[f"{cid}/pub_has_gauss"])
-    assert st[4] == float(G[f"{cid}/pub_gauss"])

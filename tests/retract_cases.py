@@ -13,18 +13,17 @@ import, so a regenerated fixture cannot bring in an ill-posed case.  Output rank
 exact.  Left unfoldings are orthonormal to 1e-12 (the bound of tests/randorth_cases.py: a Jacobi's
 rotations or its normalised rows, a few hundred flops deep at these sizes) on every case but z, whose
 kept near-zero singular values give unit columns of rounding noise."""
-import os
-
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-G = np.load(os.path.join(HERE, "golden", "retract.npz"))
+from tests.tt_cases import J_SHAPES, close, dense, load, orth_error  # noqa: F401  (re-exported)
+
+_F = load("retract.npz")
+G, _tt, train = _F.G, _F._tt, _F.train
 
 VALUE = ("f", "a", "b", "c", "d", "h", "k", "e", "w", "z", "j")   # every case with d >= 2
 FIT = ("f", "a", "b", "c", "d", "h", "k", "e", "w", "z")          # value cases that fit one workgroup's LDS
 ORTH = tuple(c for c in FIT if c != "z")
 REPRODUCE = ("a", "c", "k", "z")                                   # nothing but null directions dropped
-J_SHAPES = [(1, 4, 4, 96), (96, 4, 4, 96), (96, 4, 4, 1)]
 RTOL = 1e-11
 ORTH_TOL = 1e-12
 NOISE_MULTIPLE = 50
@@ -33,23 +32,7 @@ for _c in VALUE:
     assert NOISE_MULTIPLE * float(G[f"{_c}/noise"]) <= RTOL, (_c, float(G[f"{_c}/noise"]))
 
 
-def _tt(key):
-    return [G[f"{key}/{i}"].copy() for i in range(int(G[key + "/n"]))]
-
-
-_INPUTS = {}
 _DENSE = {}
-
-
-def train(cid):
-    """The case's input train (host arrays; a fresh copy per call)."""
-    if cid not in _INPUTS:
-        if cid == "j":  # too large to store: regenerated from the recorded seed (legacy stream: frozen)
-            rs = np.random.RandomState(int(G["j/seed"]))
-            _INPUTS[cid] = [rs.randn(*s) for s in J_SHAPES]
-        else:
-            _INPUTS[cid] = _tt(f"{cid}/in")
-    return [c.copy() for c in _INPUTS[cid]]
 
 
 def upper(cid):
@@ -65,25 +48,12 @@ def inner_and_ranks(tt):
     return ([int(np.prod(c.shape[1:-1])) for c in tt], [int(tt[0].shape[0])] + [int(c.shape[-1]) for c in tt])
 
 
-def dense(tt):
-    t = tt[0]
-    for c in tt[1:]:
-        t = np.tensordot(t, c, axes=(-1, 0))
-    return np.sum(t, axis=(0, -1))
-
-
 def reference_dense(cid):
     """The tensor the reference's output represents (computed once per case, shared, read only)."""
     if cid not in _DENSE:
         _DENSE[cid] = dense(_tt(f"{cid}/out"))
         _DENSE[cid].setflags(write=False)
     return _DENSE[cid]
-
-
-def close(a, b, rtol):
-    scale = max(np.max(np.abs(b)), 1e-300)
-    err = np.max(np.abs(np.asarray(a) - b)) / scale
-    assert err <= rtol, err
 
 
 def check_shapes(cid, res_host):
@@ -102,7 +72,4 @@ def check_result(cid, res_host):
 
 def check_left_orthonormal(res_host):
     """cores 0 .. d-2: the left unfolding (q_i n_i, q_{i+1}) has orthonormal columns"""
-    for c in res_host[:-1]:
-        u = c.reshape(-1, c.shape[-1])
-        err = np.max(np.abs(u.T @ u - np.eye(u.shape[1])))
-        assert err <= ORTH_TOL, err
+    assert orth_error(res_host) <= ORTH_TOL

@@ -94,6 +94,24 @@ def test_right_sketch_below_the_left(T, monkeypatch):
     NC.close(NC.dense(nat), NC.dense(com), 1e-11)
 
 
+def test_left_sketch_above_the_right_matches_composed(T, monkeypatch):
+    """`NC.transposed_case()`: lranks > rranks at every bond, a true truncation (well posed:
+    tests/test_host_nystroem.py); three launches, the rule's ranks, the composed path's tensor"""
+    tt, g1, g2 = (_up(T, t) for t in NC.transposed_case())
+    assert T.nystroem_lds(tt, g1, g2) >= 0
+    T.D.read(tt[0])  # uploads done
+    l0 = T.D.lib.ttk_launch_count()
+    nat = T._tt_generalised_nystroem(list(tt), g1, g2)
+    assert T.D.lib.ttk_launch_count() - l0 == 3
+    nat = T.to_host(nat)
+    assert [1] + [c.shape[-1] for c in nat] == [1, 3, 3, 1]
+    monkeypatch.setattr(T, "NATIVE_NYSTROEM", False)
+    com = T.to_host(T._tt_generalised_nystroem(list(tt), g1, g2))
+    assert [c.shape for c in nat] == [c.shape for c in com]
+    NC.close(NC.dense(nat), NC.dense(com), 1e-11)
+    T.D.check_handoffs()
+
+
 def test_three_launches_and_no_host_wait(T):
     """inputs contiguous on the device: at most three kernel launches, nothing read back"""
     tt, g1, g2 = _native(T, "g")

@@ -87,6 +87,25 @@ def test_one_launch(T):
     assert T.D.lib.ttk_launch_count() - l0 == 1
 
 
+def test_1024_threads_match_composed(T, monkeypatch):
+    """`RC.wide_case()`: a product of more than 2048 entries, so the launch has 1024 threads (every
+    fixture case runs 256); one launch, the rule's ranks, the composed path's tensor, orthonormal Q"""
+    tt, gs = (_up(T, t) for t in RC.wide_case())
+    assert T.randorth_lds(tt, gs) >= 0
+    T.D.read(tt[0])  # uploads done
+    l0 = T.D.lib.ttk_launch_count()
+    nat = T._tt_lr_random_orthogonalise(list(tt), gs)
+    assert T.D.lib.ttk_launch_count() - l0 == 1
+    nat = T.to_host(nat)
+    assert [1] + [c.shape[-1] for c in nat] == [1, 12, 12, 12, 1]
+    monkeypatch.setattr(T, "NATIVE_RANDORTH", False)
+    com = T.to_host(T._tt_lr_random_orthogonalise(list(tt), gs))
+    assert [c.shape for c in nat] == [c.shape for c in com]
+    RC.close(RC.dense(nat), RC.dense(com), 1e-11)
+    assert RC.orth_error(nat) <= 1e-12
+    T.D.check_handoffs()
+
+
 def test_two_calls_same_bits(T):
     import torch
     tt, gs = _native(T, "d")

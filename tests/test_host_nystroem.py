@@ -74,6 +74,27 @@ def test_right_sketch_below_the_left(T):
     NC.close(NC.dense(res), NC.dense(host), 1e-11)
 
 
+def test_transposed_case_is_well_posed(T):
+    """`NC.transposed_case()` (the device test of the bond SVD's transposed branch) by the rule the
+    fixture's value cases pass on import: 50 x the largest relative max-abs change of the dense result
+    over 5 reruns, every train entry multiplied by 1 + 1.1e-16 N(0, 1), stays within 1e-11"""
+    tt, g1, g2 = NC.transposed_case()
+
+    def run(train):
+        res = T.to_host(T._tt_generalised_nystroem(_up(T, train), _up(T, g1), _up(T, g2)))
+        assert [c.shape[0] for c in res[1:]] == [3, 3]
+        return NC.dense(res)
+
+    ref = run(tt)
+    nrng = np.random.default_rng(3)
+    noise = 0.0
+    for _ in range(5):
+        got = run([c * (1.0 + 1.1e-16 * nrng.standard_normal(c.shape)) for c in tt])
+        noise = max(noise, float(np.max(np.abs(got - ref)) / np.max(np.abs(ref))))
+    print("noise", noise)
+    assert NC.NOISE_MULTIPLE * noise <= NC.RTOL, noise
+
+
 @pytest.mark.parametrize("cid", NC.PUBLIC)
 def test_public_call_matches_reference_and_rng_stream(T, cid):
     tt = _up(T, NC.train(cid))

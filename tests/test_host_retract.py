@@ -99,3 +99,22 @@ def test_lds_fit_is_host_arithmetic():
     assert lds([4, 4], [1, 5, 2], [3]) == -1
     assert lds([4] * 33, [1] + [2] * 32 + [1], [2] * 32) == -1      # more than 32 cores
     assert lib.ttk_retract_lds(2, None, arr([1, 5, 1]), arr([3])) == -1
+
+
+@pytest.mark.skipif(not os.path.exists(SO), reason="libttk.so not built (run __graft_entry__.build())")
+def test_lds_bytes_of_the_benchmark_shapes():
+    """the three plans' LDS bytes at the tools/bench_*.py shapes (d = 10, middle extent 4, bond ranks r,
+    sketch ranks / bounds t, right Nystroem sketch t + 1), as measured before the planners were put on
+    shared helpers; the last column also stands in profiles/retract_d10.txt"""
+    lib = ctypes.CDLL(SO)
+    arr = lambda v: (ctypes.c_int64 * len(v))(*v)  # noqa: E731
+    for f, n in (("ttk_rand_orth_lds", 3), ("ttk_nystroem_lds", 4), ("ttk_retract_lds", 3)):
+        getattr(lib, f).restype = ctypes.c_int64
+        getattr(lib, f).argtypes = [ctypes.c_int] + [ctypes.c_void_p] * n
+    d = 10
+    for r, t, want in ((8, 4, (5152, 4448, 7232)), (12, 10, (17488, 13760, 16352)), (24, 20, (69792, 52704, 64448))):
+        inner, rk = arr([4] * d), arr([1] + [r] * (d - 1) + [1])
+        sk, sk1 = arr([1] + [t] * (d - 1) + [1]), arr([1] + [t + 1] * (d - 1) + [1])
+        got = (lib.ttk_rand_orth_lds(d, inner, rk, sk), lib.ttk_nystroem_lds(d, inner, rk, sk, sk1),
+               lib.ttk_retract_lds(d, inner, rk, arr([t] * (d - 1))))
+        assert got == want, (r, t, got)

@@ -1,5 +1,7 @@
 """Dump the outputs of a fixed set of kernel calls (extreme eigenpairs, offset-table GEMMs) on seeded
-inputs, so two library builds can be compared bit for bit:
+inputs, so two library builds can be compared bit for bit (tools/cmp_dump.py).  A second argument
+keeps only the arrays whose name starts with it and skips the sections that have none:
+`python tools/dump_kernels.py out.npz round_` dumps the three native TT roundings alone.
 
     TTK_LIB_PATH=old.so python tools/dump_kernels.py gpurun_out/a.npz
     python tools/dump_kernels.py gpurun_out/b.npz        # then compare the two files on the host"""
@@ -14,10 +16,40 @@ from ttipm_amd import dev as D  # noqa: E402
 from ttipm_amd._lib import lib  # noqa: E402
 
 
-def main(path):
+def rounding(out):
+    """The output cores of `ttk_rand_orth`, `ttk_nystroem` and `ttk_retract`: every fixture case that
+    takes the native path, the two seeded inputs of the device tests and the all-zero train."""
+    from tests import nystroem_cases as NC, randorth_cases as RO, retract_cases as RT
+    from ttipm_amd import tt_ops as T
+
+    def dump(name, launches, f, *trains):
+        trains = [T.to_device(list(t)) for t in trains]
+        D.read(trains[0][0])  # uploads done
+        l0 = lib.ttk_launch_count()
+        res = f(*trains)
+        assert lib.ttk_launch_count() - l0 == launches, name  # the native path ran
+        out[name] = np.concatenate([c.ravel() for c in T.to_host(res)])
+
+    for cid in RO.FIT:
+        dump(f"round_randorth_{cid}", 1, T._tt_lr_random_orthogonalise, RO.train(cid), RO.sketch(cid))
+    dump("round_randorth_wide", 1, T._tt_lr_random_orthogonalise, *RO.wide_case())
+    for cid in NC.FIT:
+        dump(f"round_nystroem_{cid}", 3, T._tt_generalised_nystroem, NC.train(cid), *NC.sketches(cid))
+    dump("round_nystroem_transposed", 3, T._tt_generalised_nystroem, *NC.transposed_case())
+    old, T.NATIVE_RETRACT = T.NATIVE_RETRACT, True
+    try:
+        for cid in RT.FIT:
+            dump(f"round_retract_{cid}", 1, lambda tt: T.tt_rank_retraction(tt, RT.upper(cid)), RT.train(cid))
+        rk = [1] + [5] * 5 + [1]
+        dump("round_retract_zero", 1, lambda tt: T.tt_rank_retraction(tt, [3] * 5),
+             [np.zeros((rk[i], 4, rk[i + 1])) for i in range(6)])
+    finally:
+        T.NATIVE_RETRACT = old
+
+
+def kernels(out):
     rng = np.random.default_rng(0)
     st = D._stream()
-    out = {}
     for n in [3, 5, 10, 17, 40, 63, 64, 80, 100, 127, 128, 129, 139, 150, 192, 200, 256, 257, 258, 300, 384, 512, 513,
               1000, 1900]:
         for which in (0, 1):
@@ -138,6 +170,9 @@ def main(path):
                     out[f"lgmres_{int(ineq)}_{r_}_{R_}"] = np.concatenate([D.read(x), [info["its"], info["res"]]])
                 finally:
                     lib.ttk_lgmres_set_mw_threshold(old)
+
+
+def save(path, out):
     torch.cuda.synchronize()
     import hashlib
     for k in list(out):  # big arrays as a SHA-256 digest (keeps gpurun_out small); bitwise comparison still
@@ -147,5 +182,14 @@ def main(path):
     print("dumped", len(out), "arrays to", path)
 
 
+def main(path, prefix=""):
+    out = {}
+    if "round_".startswith(prefix[:6]):
+        rounding(out)
+    if not prefix.startswith("round_"):
+        kernels(out)
+    save(path, {k: v for k, v in out.items() if k.startswith(prefix)})
+
+
 if __name__ == "__main__":
-    main(sys.argv[1])
+    main(*sys.argv[1:3])
