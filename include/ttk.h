@@ -588,6 +588,34 @@ int64_t ttk_retract_lds(int d, const int64_t *inner, const int64_t *ranks, const
 int ttk_retract(ttk_ctx ctx, int d, const double *const *cores, const int64_t *inner, const int64_t *ranks,
                 const int64_t *upper, double *const *out, int64_t *out_ranks);
 
+/* Eps-truncating TT rounding in one launch with the ranks decided on the device (`tt_rank_reduce`,
+ * `tt_psd_rank_reduce`, `tt_mask_rank_reduce`, cy_src/tt_ops_cy.pyx:179-226, :261-388): the two sweeps of
+ * ttk_retract in one workgroup, but the rank of bond i+1 is chosen in the kernel from the Jacobi's
+ * singular values s_0 >= ... >= s_{p-1}, p = min(q_i inner[i], rho_{i+1}), by the reference's rule
+ * (`prune_singular_vals`): sc[j] = sum_{t >= j} s_t^2 summed from the smallest value upward, q = the
+ * first j with sc[j] < thr2 (0 if none), at least 1, and p if sc[p-1] > thr2; thr2 = e^2 with
+ * e = (mode ? eps / 2 : eps) / sqrt(d - 1).  mode 1 (the PSD / mask variants) also accumulates the
+ * discarded tail sc[q] of every bond with q < p.  One thread decides, clamps q to [1, p] and publishes it
+ * behind one workgroup barrier; everything downstream is sized by it.  LDS and the thread count are
+ * planned from the bound ranks bound[0] = 1, bound[i+1] = min(bound[i] inner[i], rho_{i+1}), bound[d] = 1
+ * (the retraction's rule with no upper bound), which the decided ranks never exceed.  The call
+ * enqueues one launch and returns: no host read inside.  The same tensor as ttk_round's to within the
+ * eps both truncate at, in another gauge.  Fixed summation and rotation order: two calls on the same
+ * input give the same bits.
+ * cores[k]: device, contiguous (ranks[k], inner[k], ranks[k+1]) fp64, read only; ranks[0] == ranks[d]
+ * == 1; out[k]: caller-owned contiguous buffers of bound[k] inner[k] bound[k+1] doubles that overlap no
+ * input; core k comes back contiguous with its actual shape (q_k, inner[k], q_{k+1}) at the front of
+ * out[k].  info: d + 2 device doubles, written by the launch: info[k] = q_k for k = 0 .. d (exact in
+ * fp64), info[d+1] = the accumulated tail (0 in mode 0; the reference's factor is its 1/(2d)-th power).
+ * ttk_round_one_lds: the bytes of LDS the sweep needs, or -1 when the train does not fit one workgroup
+ * (at most 160 KiB and 32 cores) or the arguments are invalid -- the caller then takes ttk_round; it
+ * fills bound (d+1 entries) unless bound is NULL.  ttk_round_one validates on the host (d >= 2, every
+ * rank and extent >= 1, boundary ranks 1, no null pointer, eps finite and >= 0, mode 0 or 1, the LDS
+ * fit) and returns TTK_ERR_ARG without launching when a check fails. */
+int64_t ttk_round_one_lds(int d, const int64_t *inner, const int64_t *ranks, int64_t *bound);
+int ttk_round_one(ttk_ctx ctx, int d, const double *const *cores, const int64_t *inner, const int64_t *ranks,
+                  double eps, int mode, double *const *out, double *info);
+
 /* Dense Schur-complement local KKT solve in one call (SURVEY §8(b) `ttk_local_assemble` +
  * `ttk_dense_schur_solve`; the dense branch of `_ipm_local_solver`, src/tt_ipm.py:183-229):
  * assembles L_XI = B22 diag(inv_I), L_eq = B01, L_Z = B21 (each 'lsr,smnS,LSR->lmLrnR'), Cholesky of

@@ -25,10 +25,21 @@
 // A singular value that is exactly 0 gives a zero column of U (rows of Z^T rotated) or a zero row of M
 // (rows of Z rotated): nothing divides by it, so the all-zero train comes back as finite cores.
 //
+// `ttk_round_one` is the same two sweeps with the eps-truncating rank rule of `tt_rank_reduce` and its
+// tracked variants (cy_src/tt_ops_cy.pyx:161-226, :299-309) decided in the kernel (retract_kernel<true>):
+// after each Jacobi one thread sums the squared singular values from the smallest upward, picks q_{i+1}
+// by the reference's rule, clamps it to [1, min(m, rho_{i+1})] and publishes it in one LDS word behind
+// one workgroup barrier; from there q_{i+1}, m = q_i n_i, the orientation and the extents of out_i, M
+// and the carried core are run-time values, uniform across the workgroup.  LDS and the thread count
+// are planned from the bound ranks (no upper bound), which the run-time ranks can only undercut.  The
+// ranks and the discarded tail go to `info` on the device; the call itself reads nothing back.
+//
 // LDS holds one step's working set, not the train: two carried-core regions that the phases use in
 // turn (QR input / Q, then Z / the Jacobi's rows), one core from global memory or scratch, the
 // rotations G, M and a few small vectors.  The products are VALU fma chains, as in the siblings.
 #include <hip/hip_runtime.h>
+
+#include <cmath>
 
 #include "ttk_common.h"
 #include "ttk_internal.h"
@@ -41,20 +52,27 @@ struct RtPlan {
   int n[TT_MAXD];        // middle extents
   int r[TT_MAXD + 1];    // train bond ranks
   int rho[TT_MAXD + 1];  // bond ranks after the QR sweep
-  int q[TT_MAXD + 1];    // output bond ranks
+  int q[TT_MAXD + 1];    // output bond ranks (ttk_round_one: their bounds)
   int so[TT_MAXD];       // orthogonalised core k's offset in the scratch block (doubles), k = 1 .. d-1
   int oP0, oP1, oC, oG, oM, oT, oS;  // LDS regions (offsets in doubles, all even: 16-byte aligned)
+  int oQ;                // ttk_round_one: the run-time ranks q_0 .. q_{d-1} as doubles (each one published once)
+  int track;             // ttk_round_one: mode 1, the discarded tail sums are accumulated
+  double thr2;           // ttk_round_one: the squared per-bond threshold
+  double *info;          // ttk_round_one: d + 2 device doubles, the ranks and the tail
   const double *core[TT_MAXD];
   double *out[TT_MAXD];
 };
 
 // Validates the extents, applies the rank rule and lays out LDS and scratch.  Returns the bytes of
 // dynamic LDS, -1 when the train does not fit one workgroup (or has more than TT_MAXD cores), -2 on
-// invalid arguments.  *words: doubles of scratch for the orthogonalised cores 1 .. d-1.
-int64_t rt_plan(int d, const int64_t *inner, const int64_t *ranks, const int64_t *upper, RtPlan *p, int64_t *words) {
+// invalid arguments.  *words: doubles of scratch for the orthogonalised cores 1 .. d-1.  adapt
+// (ttk_round_one): no upper bound, q holds the bound ranks, and the plan takes one more region for the
+// run-time ranks.
+int64_t rt_plan(int d, const int64_t *inner, const int64_t *ranks, const int64_t *upper, bool adapt, RtPlan *p,
+                int64_t *words) {
   const int chk = tt_check_extents(d, inner, {ranks});
-  bool bad = chk == -2 || !upper || ranks[0] != 1 || ranks[d] != 1;
-  for (int k = 0; !bad && k + 1 < d; ++k) bad = upper[k] < 1;
+  bool bad = chk == -2 || (!adapt && !upper) || ranks[0] != 1 || ranks[d] != 1;
+  for (int k = 0; !bad && !adapt && k + 1 < d; ++k) bad = upper[k] < 1;
   if (bad) return -2;
   if (chk) return chk;
   const int64_t *n = inner, *r = ranks;
@@ -69,7 +87,7 @@ int64_t rt_plan(int d, const int64_t *inner, const int64_t *ranks, const int64_t
   q[d] = 1;
   for (int i = 0; i + 1 < d; ++i) {
     const int64_t m = q[i] * n[i];
-    int64_t v = upper[i] < m ? upper[i] : m;
+    int64_t v = (!adapt && upper[i] < m) ? upper[i] : m;
     q[i + 1] = v < rho[i + 1] ? v : rho[i + 1];
   }
   TtLayout L, S;  // LDS, scratch
@@ -95,15 +113,48 @@ int64_t rt_plan(int d, const int64_t *inner, const int64_t *ranks, const int64_t
   p->oP0 = L.take(zP), p->oP1 = L.take(zP), p->oC = L.take(zC), p->oG = L.take(zG), p->oM = L.take(zM);
   p->oT = L.take(zT), p->oS = L.take(zS);  // sv, then perm and the flags
   L.take(zS), L.take(NY_FLAGS);
+  p->oQ = adapt ? L.take(d) : 0;
   if (L.over || L.words * 8 > TT_LDS_MAX) return -1;
   *words = S.words;
   p->d = d;
+  p->track = 0, p->thr2 = 0.0, p->info = nullptr;
   p->nt = tt_threads(zP > zC ? zP : zC, pmax);
   for (int k = 0; k < d; ++k) p->n[k] = (int)n[k];
   for (int k = 0; k <= d; ++k) p->r[k] = (int)r[k], p->rho[k] = (int)rho[k], p->q[k] = (int)q[k];
   return L.words * 8;
 }
 
+// The kept rank of one bond by the reference's rule (prune_singular_vals, cy_src/tt_ops_cy.pyx:161-177) on the
+// pp singular values sv[perm[0]] >= ... : sc[j] = sum_{t >= j} sv[perm[t]]^2 summed from the smallest value
+// upward (np.cumsum's order: rounded products, rounded sums), q = the first j with sc[j] < thr2 (0 if
+// none), at least 1, and pp if sc[pp-1] > thr2; the all-zero spectrum gives 1.  *tail += sc[q] when q < pp
+// and track.  The result is clamped to [1, pp] whatever the spectrum holds (a NaN compares false).
+__device__ int rt_kept_rank(const double *sv, const int *perm, int pp, double thr2, bool track, double *tail) {
+  double sc = 0.0;
+  int q = 0;
+  for (int j = pp - 1; j >= 0; --j) {
+    const double s = sv[perm[j]];
+    sc = __dadd_rn(sc, __dmul_rn(s, s));
+    if (sc < thr2) q = j;
+  }
+  q = q < 1 ? 1 : q;
+  const double last = sv[perm[pp - 1]];
+  if (__dmul_rn(last, last) > thr2) q = pp;
+  q = q > pp ? pp : q;
+  if (track && q < pp) {
+    sc = 0.0;
+    for (int j = pp - 1; j >= q; --j) {
+      const double s = sv[perm[j]];
+      sc = __dadd_rn(sc, __dmul_rn(s, s));
+    }
+    *tail += sc;
+  }
+  return q;
+}
+
+// ADAPT false: `ttk_retract`, every q_i from the plan.  ADAPT true: `ttk_round_one`, p.q holds the bounds and
+// q_{i+1} is decided after bond i's Jacobi.
+template <bool ADAPT>
 __global__ __launch_bounds__(1024) void retract_kernel(const RtPlan p, double *scr) {
   extern __shared__ __attribute__((aligned(16))) double rt_lds[];
   double *P[2] = {rt_lds + p.oP0, rt_lds + p.oP1};
@@ -133,8 +184,12 @@ __global__ __launch_bounds__(1024) void retract_kernel(const RtPlan p, double *s
   }
   // ---- phase B: left to right; Z holds the carried core i as (q_i n_i, rho_{i+1})
   double *Z = P[cur], *A = P[cur ^ 1];
+  double *qd = rt_lds + p.oQ;  // ADAPT: q_i as decided, one word per bond
+  double tail = 0.0;           // ADAPT: thread 0's sum of the discarded tails
+  int qi = 1;
   for (int i = 0; i + 1 < d; ++i) {
-    const int m = p.q[i] * p.n[i], R = p.rho[i + 1], qn = p.q[i + 1], rest = p.n[i + 1] * p.rho[i + 2];
+    if (!ADAPT) qi = p.q[i];
+    const int m = qi * p.n[i], R = p.rho[i + 1], rest = p.n[i + 1] * p.rho[i + 2];
     const bool rowsz = m <= R;  // rotate the rows of Z, else those of Z^T
     const int pp = rowsz ? m : R, n = rowsz ? R : m;
     ro_load(C, scr + p.so[i + 1], R * rest);
@@ -143,6 +198,12 @@ __global__ __launch_bounds__(1024) void retract_kernel(const RtPlan p, double *s
       A[rowsz ? e : c * m + a] = Z[e];
     }
     const int *perm = tt_jacobi_svd(A, G, sv, pp, n);
+    int qn = p.q[i + 1];
+    if (ADAPT) {  // one thread decides, one barrier publishes: qn is uniform and 1 <= qn <= pp <= p.q[i + 1]
+      if (threadIdx.x == 0) qd[i + 1] = (double)rt_kept_rank(sv, perm, pp, p.thr2, p.track != 0, &tail);
+      __syncthreads();
+      qn = (int)qd[i + 1];
+    }
     // rows of Z:   G = U^T, A = diag(S) V^T:  out_i = G^T[:, top],        M = A[top]
     // rows of Z^T: G = V^T, A = diag(S) U^T:  out_i = (A / S)^T[:, top],  M = diag(S) G[top]
     double *oi = p.out[i];
@@ -164,9 +225,17 @@ __global__ __launch_bounds__(1024) void retract_kernel(const RtPlan p, double *s
     ro_gemm(qn, rest, R, [&](int a, int c) { return Mq[a * R + c]; }, [&](int c, int j) { return C[c * rest + j]; },
             [&](int a, int j, double v) { Z[a * rest + j] = v; });
     __syncthreads();
+    qi = qn;
   }
+  if (!ADAPT) qi = p.q[d - 1];
   double *ol = p.out[d - 1];
-  for (int e = threadIdx.x; e < p.q[d - 1] * p.n[d - 1]; e += blockDim.x) ol[e] = Z[e];
+  for (int e = threadIdx.x; e < qi * p.n[d - 1]; e += blockDim.x) ol[e] = Z[e];
+  if (ADAPT && threadIdx.x == 0) {  // the ranks (thread 0's own LDS words) and the tail
+    p.info[0] = 1.0;
+    for (int k = 1; k < d; ++k) p.info[k] = qd[k];
+    p.info[d] = 1.0;
+    p.info[d + 1] = tail;
+  }
 }
 
 }  // namespace
@@ -176,7 +245,7 @@ extern "C" {
 int64_t ttk_retract_lds(int d, const int64_t *inner, const int64_t *ranks, const int64_t *upper) {
   RtPlan p;
   int64_t words;
-  const int64_t b = rt_plan(d, inner, ranks, upper, &p, &words);
+  const int64_t b = rt_plan(d, inner, ranks, upper, false, &p, &words);
   return b < 0 ? -1 : b;
 }
 
@@ -185,7 +254,7 @@ int ttk_retract(ttk_ctx ctx, int d, const double *const *cores, const int64_t *i
   ttk::CtxScope scope(ctx);
   RtPlan p;
   int64_t words = 0;
-  const int64_t shm = (cores && out && out_ranks) ? rt_plan(d, inner, ranks, upper, &p, &words) : -2;
+  const int64_t shm = (cores && out && out_ranks) ? rt_plan(d, inner, ranks, upper, false, &p, &words) : -2;
   if (const int e = tt_plan_status(
           shm, "ttk_retract: bad arguments (d >= 2, every rank, extent and upper >= 1, boundary ranks 1)",
           "ttk_retract: the train does not fit one workgroup's LDS (ttk_retract_lds)"))
@@ -200,10 +269,51 @@ int ttk_retract(ttk_ctx ctx, int d, const double *const *cores, const int64_t *i
   }
   TtScratch w(ttk::ctx().stream);  // the orthogonalised cores 1 .. d-1
   TTK_HIP(w.alloc(words));
-  tt_lds_attr(retract_kernel, shm);
-  hipLaunchKernelGGL(retract_kernel, dim3(1), dim3(p.nt), (size_t)shm, w.st, p, w.get());
+  tt_lds_attr(retract_kernel<false>, shm);
+  hipLaunchKernelGGL(retract_kernel<false>, dim3(1), dim3(p.nt), (size_t)shm, w.st, p, w.get());
   TTK_LAUNCH_CHECK();
   for (int k = 0; k <= d; ++k) out_ranks[k] = p.q[k];
+  return TTK_OK;
+}
+
+int64_t ttk_round_one_lds(int d, const int64_t *inner, const int64_t *ranks, int64_t *bound) {
+  RtPlan p;
+  int64_t words;
+  const int64_t b = rt_plan(d, inner, ranks, nullptr, true, &p, &words);
+  if (b < 0) return -1;
+  for (int k = 0; bound && k <= d; ++k) bound[k] = p.q[k];
+  return b;
+}
+
+int ttk_round_one(ttk_ctx ctx, int d, const double *const *cores, const int64_t *inner, const int64_t *ranks,
+                  double eps, int mode, double *const *out, double *info) {
+  ttk::CtxScope scope(ctx);
+  RtPlan p;
+  int64_t words = 0;
+  const bool ok = cores && out && info && eps >= 0.0 && eps <= 1.79769313486231570e308 && (mode == 0 || mode == 1);
+  const int64_t shm = ok ? rt_plan(d, inner, ranks, nullptr, true, &p, &words) : -2;
+  if (const int e = tt_plan_status(shm,
+                                   "ttk_round_one: bad arguments (d >= 2, every rank and extent >= 1, boundary ranks "
+                                   "1, eps finite and >= 0, mode 0 or 1)",
+                                   "ttk_round_one: the train does not fit one workgroup's LDS (ttk_round_one_lds)"))
+    return e;
+  for (int k = 0; k < d; ++k) {
+    if (!cores[k] || !out[k]) {
+      ttk::set_error("ttk_round_one: null core %d", k);
+      return TTK_ERR_ARG;
+    }
+    p.core[k] = cores[k];
+    p.out[k] = out[k];
+  }
+  const double e = (mode ? eps / 2.0 : eps) / std::sqrt((double)(d - 1));
+  p.thr2 = e * e;
+  p.track = mode;
+  p.info = info;
+  TtScratch w(ttk::ctx().stream);  // the orthogonalised cores 1 .. d-1
+  TTK_HIP(w.alloc(words));
+  tt_lds_attr(retract_kernel<true>, shm);
+  hipLaunchKernelGGL(retract_kernel<true>, dim3(1), dim3(p.nt), (size_t)shm, w.st, p, w.get());
+  TTK_LAUNCH_CHECK();
   return TTK_OK;
 }
 

@@ -338,12 +338,64 @@ def _native_round(tt, eps, mode):
     return tt, (None if np.isnan(tail.value) else tail.value)
 
 
+ROUND_ONE = os.environ.get("TTIPM_ROUND_ONE", "0") == "1"
+
+
+def _round_one_plan(tt):
+    """(inner, ranks, bound) for `ttk_round_one` -- the ctypes extents of the train and the library's bound
+    ranks -- or None when the train does not fit one workgroup's LDS."""
+    d = len(tt)
+    if d < 2:
+        return None
+    inner, ranks = _tt_extents(tt)
+    bound = (ctypes.c_int64 * (d + 1))()
+    if D.lib.ttk_round_one_lds(d, inner, ranks, bound) < 0:
+        return None
+    return inner, ranks, bound
+
+
+def round_one_lds(tt):
+    """Bytes of LDS `ttk_round_one` needs for this train, -1 if it does not fit one workgroup (`ttk_round`
+    then runs)."""
+    if len(tt) < 2:
+        return -1
+    return int(D.lib.ttk_round_one_lds(len(tt), *_tt_extents(tt), None))
+
+
+def _round_one(tt, eps, mode, plan=None):
+    """`ttk_round_one`: the QR sweep and the truncating Jacobi-SVD sweep in one launch of one workgroup, the
+    ranks decided in the kernel, into one fresh buffer sized by the bound ranks (the output cores are views
+    of its front parts).  One host read, after the launch: the d + 1 ranks and the tail.  The caller's
+    tensors are never written and the list is rebound in place.  Returns (tt, tail factor or None)."""
+    d = len(tt)
+    inner, ranks, bound = plan or _round_one_plan(tt)
+    assert list(bound) == retraction_ranks(inner, ranks, [1 << 62] * (d - 1)), list(bound)
+    outs, _ = _packed_out(tt, list(bound), inner)
+    keep = [D.contig(c) for c in tt]  # the contiguous inputs stay alive until the call is enqueued
+    P = ctypes.c_void_p * d
+    info = D.empty(d + 2)
+    D._stream()
+    D.check(D.lib.ttk_round_one(D.ctx(), d, P(*[c.data_ptr() for c in keep]), inner, ranks, float(eps), mode,
+                                P(*[o.data_ptr() for o in outs]), info.data_ptr()), "round_one")
+    got = D.read(info)
+    q = [int(v) for v in got[:d + 1]]
+    tt[:] = [o[:q[k] * inner[k] * q[k + 1]].view(q[k], *tt[k].shape[1:-1], q[k + 1]) for k, o in enumerate(outs)]
+    return tt, (pow(float(got[d + 1]), 1.0 / (2 * d)) if mode else None)
+
+
 def tt_rank_reduce(tt, eps=1e-18):
-    """`cy_src/tt_ops_cy.pyx:179-226`: QR sweep + left-to-right truncated-SVD sweep."""
+    """`cy_src/tt_ops_cy.pyx:179-226`: QR sweep + left-to-right truncated-SVD sweep.  With TTIPM_ROUND_ONE=1,
+    on the GPU and for a train that fits (`round_one_lds`): one launch and one host read (`ttk_round_one`),
+    the same tensor in another gauge.  Off by default: the whole-solve goldens are pinned to the current
+    path's arithmetic."""
     d = len(tt)
     rk = [1] + tt_ranks(tt) + [1]
     if d == 1 or all(r == 1 for r in rk):
         return tt
+    if ROUND_ONE and D.DEV.type == "cuda":
+        plan = _round_one_plan(tt)
+        if plan is not None:
+            return _round_one(tt, eps, 0, plan)[0]
     if NATIVE_ROUND and D.DEV.type == "cuda":
         return _native_round(tt, eps, 0)[0]
     eps = eps / np.sqrt(d - 1)
@@ -359,6 +411,10 @@ def _tail_rank_reduce(tt, eps):
     rk = [1] + tt_ranks(tt) + [1]
     if d == 1 or all(r == 1 for r in rk):
         return tt, None
+    if ROUND_ONE and D.DEV.type == "cuda":
+        plan = _round_one_plan(tt)
+        if plan is not None:
+            return _round_one(tt, eps, 1, plan)
     if NATIVE_ROUND and D.DEV.type == "cuda":
         return _native_round(tt, eps, 1)
     eps = eps / 2.0

@@ -3,6 +3,16 @@ like the IPM's: d cores of (r, 2, 2, r).  Prints per-call latency and a digest o
 so two libraries (TTK_LIB_PATH) can be compared for speed and for identical bits.
 
     python tools/bench_round.py [reps]
+
+`one` times the one-launch path (`ttk_round_one`, TTIPM_ROUND_ONE=1) against `ttk_round` in the same run, at
+the shapes of tools/bench_retract.py (d = 10, cores (r,2,2,R), ranks 8 / 12 / 24): `tt_rank_reduce` at eps = 1e-3
+(the row of profiles/retract_d10.txt, which keeps the ranks at 8 and 12), and `tt_rank_reduce` and the tracked
+`_tail_rank_reduce` at eps = 1e-2 ||T||, where the ranks drop.  The two paths alternate round by round so
+that drift of the shared host hits both alike; each figure is a host clock around `reps` calls that end in
+a device synchronise, per call; the table gives the median over the rounds and their min / max, next to
+the launches and host waits per call and what was computed (ranks, distance from the input).
+
+    python tools/bench_round.py one [reps] [rounds]
 """
 import hashlib
 import os
@@ -51,5 +61,71 @@ def main():
     print("digest", h.hexdigest()[:16], flush=True)
 
 
+def bench_one(d, r, eps_rel, tracked, reps, rounds):
+    rng = np.random.default_rng(5)
+    ranks = [1] + [r] * (d - 1) + [1]
+    base = [D.from_numpy(rng.standard_normal((ranks[k], 2, 2, ranks[k + 1])) * (0.5 ** np.arange(ranks[k + 1])))
+            for k in range(d)]
+    lds = T.round_one_lds(base)
+    assert lds >= 0
+    eps = eps_rel * T.tt_norm(base) if eps_rel else 1e-3
+
+    def call(switch):
+        def f():
+            T.ROUND_ONE = switch
+            return T._tail_rank_reduce(list(base), eps)[0] if tracked else T.tt_rank_reduce(list(base), eps)
+        return f
+
+    what = (("ttk_round (the default)", call(False)), ("ttk_round_one", call(True)))
+    ref = T.tt_to_tensor(base)
+    info = {}
+    for name, f in what:
+        out = f()
+        torch.cuda.synchronize()
+        l0, s0 = D.lib.ttk_launch_count(), D.lib.ttk_sync_count()
+        f()
+        torch.cuda.synchronize()
+        info[name] = (T.tt_ranks(out), D.lib.ttk_launch_count() - l0, D.lib.ttk_sync_count() - s0,
+                      float(np.linalg.norm(T.tt_to_tensor(out) - ref) / np.linalg.norm(ref)))
+        for _ in range(20):  # warm-up of every shape the timed window uses
+            f()
+    torch.cuda.synchronize()
+    times = {name: [] for name, _ in what}
+    for _ in range(rounds):
+        for name, f in what:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                f()
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) / reps * 1e6)
+    T.ROUND_ONE = False
+    fn = "_tail_rank_reduce" if tracked else "tt_rank_reduce"
+    print(f"d={d} ranks {r} cores (r,2,2,R) {fn} eps {eps:g}; LDS {lds} bytes; {reps} calls x {rounds} rounds, "
+          f"us per call", flush=True)
+    for name, _ in what:
+        t = np.array(times[name])
+        rk, nl, ns, err = info[name]
+        print(f"{name:24s} median {np.median(t):8.1f}  min {t.min():8.1f}  max {t.max():8.1f}  launches {nl:3d}  "
+              f"host waits {ns:2d}  |out - in|/|in| {err:.2e}  ranks {rk}", flush=True)
+    old, new = (np.array(times[name]) for name, _ in what)
+    spread = max(old.max() - old.min(), new.max() - new.min())
+    gap = float(np.median(old) - np.median(new))
+    print(f"ttk_round_one: {np.median(old) / np.median(new):.2f}x ttk_round (medians {gap:.1f} us apart, min-max "
+          f"spread {spread:.1f} us: {'beyond' if abs(gap) > spread else 'within'} the spread)\n", flush=True)
+
+
+def main_one(argv):
+    reps = int(argv[0]) if argv else 100
+    rounds = int(argv[1]) if len(argv) > 1 else 7
+    assert torch.cuda.is_available(), "bench_round needs an MI355X"
+    for r in (8, 12, 24):
+        for eps_rel, tracked in ((0, False), (1e-2, False), (1e-2, True)):
+            bench_one(10, r, eps_rel, tracked, reps, rounds)
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:2] == ["one"]:
+        main_one(sys.argv[2:])
+    else:
+        main()

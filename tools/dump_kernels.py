@@ -17,7 +17,7 @@ from ttipm_amd._lib import lib  # noqa: E402
 
 
 def rounding(out):
-    """The output cores of `ttk_rand_orth`, `ttk_nystroem` and `ttk_retract`: every fixture case that
+    """The output cores of `ttk_rand_orth`, `ttk_nystroem`, `ttk_retract` and `ttk_round_one`: every fixture case that
     takes the native path, the two seeded inputs of the device tests and the all-zero train."""
     from tests import nystroem_cases as NC, randorth_cases as RO, retract_cases as RT
     from ttipm_amd import tt_ops as T
@@ -45,6 +45,13 @@ def rounding(out):
              [np.zeros((rk[i], 4, rk[i + 1])) for i in range(6)])
     finally:
         T.NATIVE_RETRACT = old
+    from tests import round_one_cases as R1
+    old, T.ROUND_ONE = T.ROUND_ONE, True
+    try:
+        for cid in R1.ORTH:  # `ttk_round_one` and the copy kernel of its one read
+            dump(f"round_one_{cid}", 2, lambda tt: T.tt_rank_reduce(tt, R1.eps(cid)), R1.train(cid))
+    finally:
+        T.ROUND_ONE = old
 
 
 def kernels(out):
