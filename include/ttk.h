@@ -616,6 +616,44 @@ int64_t ttk_round_one_lds(int d, const int64_t *inner, const int64_t *ranks, int
 int ttk_round_one(ttk_ctx ctx, int d, const double *const *cores, const int64_t *inner, const int64_t *ranks,
                   double eps, int mode, double *const *out, double *info);
 
+/* ttk_round_one on a weighted sum of trains that is never built: S = sum_{j < nterms} coef_j op_j(T_j),
+ * 1 <= nterms <= 4, the operand of the reference's `tt_rank_reduce(tt_add(a, tt_scale(alpha, b)))`,
+ * `tt_sub`, `tt_sum` and `_tt_symmetrise` (src/tt_ops.py:321-328, src/tt_ipm.py:477-485, :612-640,
+ * cy_src/tt_ops_cy.pyx:94-114, :243-258).  S has the bond ranks R_k = sum_j ranks_j[k] for 0 < k < d and
+ * R_0 = R_d = 1; term j owns the rows [A_j, A_j + ranks_j[k]) and the columns [B_j, B_j + ranks_j[k+1]) of
+ * core k, A_j and B_j the prefix sums in term order: core 0 is the terms side by side along the last
+ * axis, each times its weight, core d-1 the terms stacked along the first axis, an interior core block
+ * diagonal, everything else exactly 0.0 (`tt_add`'s layout).  The kernel's two loads write these cores
+ * straight into LDS, every element once by the thread that owns it; they never exist in global memory.
+ * coef_j is applied once, to the term's core 0, as one rounded product; a weight of exactly 1.0 copies
+ * the bits.  op_j is the identity (transpose 0) or the swap of the two middle indices (transpose 1):
+ * rows[k] is the first middle extent n1_k of S's core k, n2_k = inner[k] / rows[k], a transposed term
+ * stores its core k as (r, n2_k, n1_k, r') and element (a, i, j, b) of op_j(T_j) is its stored
+ * (a, j, i, b).  rows may be NULL when no term is transposed.  Terms may alias each other; the inputs are
+ * read only.  Everything after the loads is ttk_round_one on S: the plan (LDS bytes, thread count, bound
+ * ranks) is ttk_round_one_lds(d, inner, R), the same rank rule, eps, mode, out and info, one launch, no
+ * host read, the same bits on two calls, and for one term of weight 1 the bits of ttk_round_one.
+ * ttk_sum_term: cores, d device pointers to contiguous (ranks[k], inner[k], ranks[k+1]) fp64 cores (a
+ * transposed term: (ranks[k], n2_k, n1_k, ranks[k+1])); ranks, d+1 entries, ranks[0] == ranks[d] == 1;
+ * coef finite; transpose 0 or 1.  out[k]: bound[k] inner[k] bound[k+1] doubles that overlap no input.
+ * ttk_sum_round_one_lds: the bytes of LDS, or -1 when the sum does not fit one workgroup (at most
+ * 160 KiB and 32 cores) or the arguments are invalid -- the caller then builds the sum and takes
+ * ttk_round; it fills sum_ranks and bound (d+1 entries each) unless NULL.  ttk_sum_round_one validates
+ * on the host (whatever ttk_round_one checks, for every term; nterms in 1 .. 4; no null term table,
+ * cores table or core; coef finite; transpose 0 or 1; rows given if a term is transposed, and every
+ * rows[k] >= 1 dividing inner[k]; the LDS fit) and returns TTK_ERR_ARG without launching when a check
+ * fails. */
+typedef struct {
+  const double *const *cores;
+  const int64_t *ranks;
+  double coef;
+  int transpose;
+} ttk_sum_term;
+int64_t ttk_sum_round_one_lds(int d, const int64_t *inner, int nterms, const ttk_sum_term *terms,
+                              int64_t *sum_ranks, int64_t *bound);
+int ttk_sum_round_one(ttk_ctx ctx, int d, const int64_t *inner, const int64_t *rows, int nterms,
+                      const ttk_sum_term *terms, double eps, int mode, double *const *out, double *info);
+
 /* Dense Schur-complement local KKT solve in one call (SURVEY §8(b) `ttk_local_assemble` +
  * `ttk_dense_schur_solve`; the dense branch of `_ipm_local_solver`, src/tt_ipm.py:183-229):
  * assembles L_XI = B22 diag(inv_I), L_eq = B01, L_Z = B21 (each 'lsr,smnS,LSR->lmLrnR'), Cholesky of

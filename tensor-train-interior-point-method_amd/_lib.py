@@ -91,6 +91,8 @@ _SIGS = {
     "ttk_retract": (i32, [vp, i32, vp, vp, vp, vp, vp, vp]),
     "ttk_round_one_lds": (i64, [i32, vp, vp, vp]),
     "ttk_round_one": (i32, [vp, i32, vp, vp, vp, f64, i32, vp, vp]),
+    "ttk_sum_round_one_lds": (i64, [i32, vp, i32, vp, vp, vp]),
+    "ttk_sum_round_one": (i32, [vp, i32, vp, vp, i32, vp, f64, i32, vp, vp]),
     "ttk_dense_schur_solve": (i32, [vp, i64, i64, i64, vp, vp, vp, vp, vp]),
     "ttk_dense_schur_solve_ineq": (i32, [vp, i64, i64, i64, vp, vp, vp, vp]),
     "ttk_fused_set_mfma": (i32, [i32]),
@@ -156,6 +158,11 @@ TTK_OK, TTK_ERR_ARG, TTK_ERR_HIP, TTK_ERR_NOT_PD, TTK_ERR_SINGULAR, TTK_ERR_NOT_
 (KNOB_FUSED_APPLY, KNOB_FUSED_MFMA, KNOB_SPLITK, KNOB_SPLITK_MINK, KNOB_LGMRES_MW_MIN, KNOB_MFMA_CSPLIT, KNOB_APPLY_DUAL,
  KNOB_RCOND_EXACT, KNOB_SCHUR_ONE, KNOB_ARNOLDI_ONE, KNOB_SCHUR_PREP, KNOB_SPLITK_FUSED, KNOB_TRI_HOIST,
  KNOB_TRI_ONE, KNOB_TRI_PERSIST, KNOB_SYEV_WAVES8, KNOB_BT_STAGE) = range(17)
+
+
+class SumTerm(ctypes.Structure):
+    """`ttk_sum_term` (include/ttk.h): one term of `ttk_sum_round_one`"""
+    _fields_ = [("cores", vp), ("ranks", vp), ("coef", f64), ("transpose", i32)]
 
 
 class TTKError(RuntimeError):

@@ -26,13 +26,21 @@
 // (rows of Z rotated): nothing divides by it, so the all-zero train comes back as finite cores.
 //
 // `ttk_round_one` is the same two sweeps with the eps-truncating rank rule of `tt_rank_reduce` and its
-// tracked variants (cy_src/tt_ops_cy.pyx:161-226, :299-309) decided in the kernel (retract_kernel<true>):
+// tracked variants (cy_src/tt_ops_cy.pyx:161-226, :299-309) decided in the kernel (retract_kernel<true, RtPlan>):
 // after each Jacobi one thread sums the squared singular values from the smallest upward, picks q_{i+1}
 // by the reference's rule, clamps it to [1, min(m, rho_{i+1})] and publishes it in one LDS word behind
 // one workgroup barrier; from there q_{i+1}, m = q_i n_i, the orientation and the extents of out_i, M
 // and the carried core are run-time values, uniform across the workgroup.  LDS and the thread count
 // are planned from the bound ranks (no upper bound), which the run-time ranks can only undercut.  The
 // ranks and the discarded tail go to `info` on the device; the call itself reads nothing back.
+//
+// `ttk_sum_round_one` is `ttk_round_one` on the weighted sum S = sum_j c_j op_j(T_j) of up to RS_TERMS trains
+// (`tt_add` of `tt_scale`d and transposed trains, cy_src/tt_ops_cy.pyx:94-114, :243-258) that is never built:
+// the kernel reads its input cores in exactly two places, and there the summed core -- term j's block at the
+// prefix-sum offsets of its ranks, times c_j in core 0, its two middle indices swapped where asked, exactly 0.0
+// elsewhere -- is written straight into the LDS region the plain load fills, each element once by the thread
+// that owns it (rt_load_core).  The plan is the one of the summed ranks; everything after the loads is
+// retract_kernel<true, RtPlan>'s code.
 //
 // LDS holds one step's working set, not the train: two carried-core regions that the phases use in
 // turn (QR input / Q, then Z / the Jacobi's rows), one core from global memory or scratch, the
@@ -62,6 +70,20 @@ struct RtPlan {
   const double *core[TT_MAXD];
   double *out[TT_MAXD];
 };
+
+constexpr int RS_TERMS = 4;  // terms of a summed train
+
+// `ttk_sum_round_one`: the plan of the summed train S (p.r its ranks, p.core unused) and the terms.
+struct RtSumArg {
+  RtPlan p;
+  int nterms;
+  int tr[RS_TERMS];             // 1: the term stores core k as (r, n2_k, n1_k, r')
+  int n1[TT_MAXD];              // first middle extent of S's core k (n_k where no term is transposed)
+  int r[RS_TERMS][TT_MAXD + 1]; // the terms' bond ranks
+  double coef[RS_TERMS];        // applied to the term's core 0
+  const double *core[RS_TERMS][TT_MAXD];
+};
+static_assert(sizeof(RtSumArg) < 4096, "the plan and the terms travel as one kernel argument");
 
 // Validates the extents, applies the rank rule and lays out LDS and scratch.  Returns the bytes of
 // dynamic LDS, -1 when the train does not fit one workgroup (or has more than TT_MAXD cores), -2 on
@@ -152,21 +174,60 @@ __device__ int rt_kept_rank(const double *sv, const int *perm, int pp, double th
   return q;
 }
 
+__device__ __forceinline__ const RtPlan &rt_plan_of(const RtPlan &a) { return a; }
+__device__ __forceinline__ const RtPlan &rt_plan_of(const RtSumArg &a) { return a.p; }
+
+// Core k of the train, (r_k, n_k, r_{k+1}) row-major, into dst.  No barrier: the caller's next one publishes it.
+__device__ __forceinline__ void rt_load_core(double *dst, const RtPlan &a, int k) {
+  ro_load(dst, a.core[k], a.r[k] * a.n[k] * a.r[k + 1]);
+}
+
+// Core k of the summed train: element (a, i, b) belongs to the one term whose row range holds a (every term
+// at k = 0, where R_0 = 1) and whose column range holds b (every term at k = d-1), and is 0.0 if there is
+// none.  Each destination element is written once, by the thread that owns it.
+__device__ __forceinline__ void rt_load_core(double *dst, const RtSumArg &s, int k) {
+  const int n = s.p.n[k], R1 = s.p.r[k + 1], nR1 = n * R1, total = s.p.r[k] * nR1;
+  const int n1 = s.n1[k], n2 = n / n1;
+  const bool first = k == 0, last = k == s.p.d - 1;
+  for (int e = threadIdx.x; e < total; e += blockDim.x) {
+    const int a = e / nR1, rem = e - a * nR1, i = rem / R1, b = rem - i * R1;
+    double v = 0.0;
+    int A = 0, B = 0;
+    for (int j = 0; j < s.nterms; ++j) {
+      const int ra = s.r[j][k], rb = s.r[j][k + 1];
+      const int la = first ? 0 : a - A, lb = last ? 0 : b - B;
+      if (la >= 0 && la < ra && lb >= 0 && lb < rb) {
+        int mid = i;
+        if (s.tr[j]) {
+          const int i1 = i / n2, i2 = i - i1 * n2;
+          mid = i2 * n1 + i1;
+        }
+        const double x = s.core[j][k][(la * n + mid) * rb + lb];
+        v = (first && s.coef[j] != 1.0) ? __dmul_rn(s.coef[j], x) : x;
+      }
+      A += ra, B += rb;
+    }
+    dst[e] = v;
+  }
+}
+
 // ADAPT false: `ttk_retract`, every q_i from the plan.  ADAPT true: `ttk_round_one`, p.q holds the bounds and
-// q_{i+1} is decided after bond i's Jacobi.
-template <bool ADAPT>
-__global__ __launch_bounds__(1024) void retract_kernel(const RtPlan p, double *scr) {
+// q_{i+1} is decided after bond i's Jacobi.  Arg: RtPlan, the cores as they lie in global memory, or RtSumArg,
+// the cores of the summed train (`ttk_sum_round_one`); it only enters the two rt_load_core calls.
+template <bool ADAPT, class Arg>
+__global__ __launch_bounds__(1024) void retract_kernel(const Arg arg, double *scr) {
+  const RtPlan &p = rt_plan_of(arg);
   extern __shared__ __attribute__((aligned(16))) double rt_lds[];
   double *P[2] = {rt_lds + p.oP0, rt_lds + p.oP1};
   double *C = rt_lds + p.oC, *G = rt_lds + p.oG, *Mq = rt_lds + p.oM, *tau = rt_lds + p.oT, *sv = rt_lds + p.oS;
   const int d = p.d;
   int cur = 0;
   // ---- phase A: right to left; P[cur] holds the carried core k as (r_k, n_k rho_{k+1})
-  ro_load(P[0], p.core[d - 1], p.r[d - 1] * p.n[d - 1]);
+  rt_load_core(P[0], arg, d - 1);
   for (int k = d - 1; k >= 1; --k) {
     const int rk = p.r[k], m = p.n[k] * p.rho[k + 1], kk = p.rho[k], rows = p.r[k - 1] * p.n[k - 1];
     double *Y = P[cur], *Qc = P[cur ^ 1];
-    ro_load(C, p.core[k - 1], rows * rk);
+    rt_load_core(C, arg, k - 1);
     __syncthreads();
     // the carried core's rows are the columns of its transpose (m x r_k, column-major)
     ro_householder(Y, m, rk, tau);
@@ -238,6 +299,42 @@ __global__ __launch_bounds__(1024) void retract_kernel(const RtPlan p, double *s
   }
 }
 
+// `ttk_sum_round_one`'s checks on the terms and the plan of the summed train: the bytes of dynamic LDS, -1 when
+// the sum does not fit one workgroup, -2 on invalid arguments.  sum: the summed ranks, d + 1 entries.
+int64_t rs_plan(int d, const int64_t *inner, int nterms, const ttk_sum_term *terms, RtSumArg *a, int64_t *words,
+                int64_t *sum) {
+  if (nterms < 1 || nterms > RS_TERMS || !terms) return -2;
+  bool big = false;
+  for (int j = 0; j < nterms; ++j) {
+    const ttk_sum_term &t = terms[j];
+    if (!t.cores || !std::isfinite(t.coef) || (t.transpose != 0 && t.transpose != 1)) return -2;
+    const int chk = tt_check_extents(d, inner, {t.ranks});
+    if (chk == -2 || t.ranks[0] != 1 || t.ranks[d] != 1) return -2;
+    big |= chk != 0;
+  }
+  if (big) return -1;  // d <= TT_MAXD and every rank <= TT_CAP from here on
+  for (int j = 0; j < nterms; ++j)
+    for (int k = 0; k < d; ++k)
+      if (!terms[j].cores[k]) return -2;
+  sum[0] = sum[d] = 1;
+  for (int k = 1; k < d; ++k) {
+    sum[k] = 0;
+    for (int j = 0; j < nterms; ++j) sum[k] += terms[j].ranks[k];
+  }
+  const int64_t shm = rt_plan(d, inner, sum, nullptr, true, &a->p, words);
+  if (shm < 0) return shm;
+  a->nterms = nterms;
+  for (int j = 0; j < RS_TERMS; ++j) {
+    const bool on = j < nterms;
+    a->tr[j] = on ? terms[j].transpose : 0;
+    a->coef[j] = on ? terms[j].coef : 0.0;
+    for (int k = 0; k <= d; ++k) a->r[j][k] = on ? (int)terms[j].ranks[k] : 0;
+    for (int k = 0; k < d; ++k) a->core[j][k] = on ? terms[j].cores[k] : nullptr;
+  }
+  for (int k = 0; k < d; ++k) a->n1[k] = (int)inner[k], a->p.core[k] = nullptr;
+  return shm;
+}
+
 }  // namespace
 
 extern "C" {
@@ -269,8 +366,8 @@ int ttk_retract(ttk_ctx ctx, int d, const double *const *cores, const int64_t *i
   }
   TtScratch w(ttk::ctx().stream);  // the orthogonalised cores 1 .. d-1
   TTK_HIP(w.alloc(words));
-  tt_lds_attr(retract_kernel<false>, shm);
-  hipLaunchKernelGGL(retract_kernel<false>, dim3(1), dim3(p.nt), (size_t)shm, w.st, p, w.get());
+  tt_lds_attr(retract_kernel<false, RtPlan>, shm);
+  hipLaunchKernelGGL((retract_kernel<false, RtPlan>), dim3(1), dim3(p.nt), (size_t)shm, w.st, p, w.get());
   TTK_LAUNCH_CHECK();
   for (int k = 0; k <= d; ++k) out_ranks[k] = p.q[k];
   return TTK_OK;
@@ -311,8 +408,62 @@ int ttk_round_one(ttk_ctx ctx, int d, const double *const *cores, const int64_t 
   p.info = info;
   TtScratch w(ttk::ctx().stream);  // the orthogonalised cores 1 .. d-1
   TTK_HIP(w.alloc(words));
-  tt_lds_attr(retract_kernel<true>, shm);
-  hipLaunchKernelGGL(retract_kernel<true>, dim3(1), dim3(p.nt), (size_t)shm, w.st, p, w.get());
+  tt_lds_attr(retract_kernel<true, RtPlan>, shm);
+  hipLaunchKernelGGL((retract_kernel<true, RtPlan>), dim3(1), dim3(p.nt), (size_t)shm, w.st, p, w.get());
+  TTK_LAUNCH_CHECK();
+  return TTK_OK;
+}
+
+int64_t ttk_sum_round_one_lds(int d, const int64_t *inner, int nterms, const ttk_sum_term *terms, int64_t *sum_ranks,
+                              int64_t *bound) {
+  RtSumArg a;
+  int64_t words, sum[TT_MAXD + 1];
+  const int64_t b = rs_plan(d, inner, nterms, terms, &a, &words, sum);
+  if (b < 0) return -1;
+  for (int k = 0; sum_ranks && k <= d; ++k) sum_ranks[k] = sum[k];
+  for (int k = 0; bound && k <= d; ++k) bound[k] = a.p.q[k];
+  return b;
+}
+
+int ttk_sum_round_one(ttk_ctx ctx, int d, const int64_t *inner, const int64_t *rows, int nterms,
+                      const ttk_sum_term *terms, double eps, int mode, double *const *out, double *info) {
+  ttk::CtxScope scope(ctx);
+  RtSumArg a;
+  int64_t words = 0, sum[TT_MAXD + 1];
+  const bool ok = out && info && eps >= 0.0 && eps <= 1.79769313486231570e308 && (mode == 0 || mode == 1);
+  const int64_t shm = ok ? rs_plan(d, inner, nterms, terms, &a, &words, sum) : -2;
+  if (const int e = tt_plan_status(
+          shm,
+          "ttk_sum_round_one: bad arguments (d >= 2, 1 to 4 terms, every rank and extent >= 1, boundary ranks 1, no "
+          "null pointer, coef finite, transpose 0 or 1, eps finite and >= 0, mode 0 or 1)",
+          "ttk_sum_round_one: the sum does not fit one workgroup's LDS (ttk_sum_round_one_lds)"))
+    return e;
+  bool transposed = false;
+  for (int j = 0; j < nterms; ++j) transposed |= terms[j].transpose != 0;
+  if (transposed && !rows) {
+    ttk::set_error("ttk_sum_round_one: a transposed term needs rows");
+    return TTK_ERR_ARG;
+  }
+  for (int k = 0; k < d; ++k) {
+    if (rows && (rows[k] < 1 || inner[k] % rows[k] != 0)) {
+      ttk::set_error("ttk_sum_round_one: rows[%d] does not divide inner[%d]", k, k);
+      return TTK_ERR_ARG;
+    }
+    if (!out[k]) {
+      ttk::set_error("ttk_sum_round_one: null out %d", k);
+      return TTK_ERR_ARG;
+    }
+    if (rows) a.n1[k] = (int)rows[k];
+    a.p.out[k] = out[k];
+  }
+  const double e = (mode ? eps / 2.0 : eps) / std::sqrt((double)(d - 1));
+  a.p.thr2 = e * e;
+  a.p.track = mode;
+  a.p.info = info;
+  TtScratch w(ttk::ctx().stream);  // the orthogonalised cores 1 .. d-1
+  TTK_HIP(w.alloc(words));
+  tt_lds_attr(retract_kernel<true, RtSumArg>, shm);
+  hipLaunchKernelGGL((retract_kernel<true, RtSumArg>), dim3(1), dim3(a.p.nt), (size_t)shm, w.st, a, w.get());
   TTK_LAUNCH_CHECK();
   return TTK_OK;
 }

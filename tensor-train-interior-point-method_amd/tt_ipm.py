@@ -668,16 +668,63 @@ def tt_infeasible_newton_system(lhs, C, X, Y, Z, Tt, L, Ladj, b, mask, st):
     return lhs, rhs, st
 
 
+def _fused_sum(trains, coeffs, transposed, e, mode=0, mask=None, draws=()):
+    """round(sum_j coeffs[j] op_j(trains[j])) by `ttk_sum_round_one` (TTIPM_SUM_ROUND_ONE=1, on the GPU, a sum
+    that fits), else None: the caller then runs its expression as it stands -- the same library calls in the
+    same order, the same random draws.  mode 0 / 1 / 2: `tt_rank_reduce` / the PSD / the mask variant.  draws:
+    the lengths of the trains the replaced `tt_scale` calls would scale, in call order; the same `randint`s
+    are drawn (`cy_src/tt_ops_cy.pyx:94-114`), so the MT19937 stream stays aligned with the reference's."""
+    res = T._sum_native(trains, coeffs, transposed, e, min(mode, 1))
+    if res is None:
+        return None
+    for n in draws:
+        _rng.R().randint(0, n)
+    tt, factor = res
+    return tt if mode == 0 else T._psd_correct(tt, factor) if mode == 1 else T._mask_correct(tt, mask, factor)
+
+
+def _f32(alpha):
+    """the weight `tt_scale` applies"""
+    return float(np.float32(alpha))
+
+
 def _tt_symmetrise(M, e):
-    return T.tt_rank_reduce(T.tt_scale(0.5, T.tt_add(M, T.tt_transpose(M))), eps=e)
+    res = _fused_sum([M, M], [0.5, 0.5], [False, True], e, 0, draws=(len(M),))
+    return res if res is not None else T.tt_rank_reduce(T.tt_scale(0.5, T.tt_add(M, T.tt_transpose(M))), eps=e)
 
 
 def _tt_psd_symmetrise(M, e):
-    return T.tt_psd_rank_reduce(T.tt_scale(0.5, T.tt_add(M, T.tt_transpose(M))), eps=e)
+    res = _fused_sum([M, M], [0.5, 0.5], [False, True], e, 1, draws=(len(M),))
+    return res if res is not None else T.tt_psd_rank_reduce(T.tt_scale(0.5, T.tt_add(M, T.tt_transpose(M))), eps=e)
 
 
 def _tt_mask_symmetrise(M, mask, e):
-    return T.tt_mask_rank_reduce(T.tt_scale(0.5, T.tt_add(M, T.tt_transpose(M))), mask, eps=e)
+    res = _fused_sum([M, M], [0.5, 0.5], [False, True], e, 2, mask, draws=(len(M),))
+    return res if res is not None else T.tt_mask_rank_reduce(T.tt_scale(0.5, T.tt_add(M, T.tt_transpose(M))), mask,
+                                                             eps=e)
+
+
+def _tt_step_symmetrise(X, alpha, DX, e, mode=0, mask=None):
+    """`_tt_symmetrise(T.tt_add(X, T.tt_scale(alpha, DX)), e)` (mode 1 / 2: the PSD / mask variant); fused, one
+    4-term call on X, DX and their transposes with the weights 0.5 and 0.5 float32(alpha)"""
+    w = 0.5 * _f32(alpha)
+    res = _fused_sum([X, DX, X, DX], [0.5, w, 0.5, w], [False, False, True, True], e, mode, mask,
+                     draws=(len(DX), len(X)))
+    if res is not None:
+        return res
+    M = T.tt_add(X, T.tt_scale(alpha, DX))
+    if mode == 0:
+        return _tt_symmetrise(M, e)
+    return _tt_psd_symmetrise(M, e) if mode == 1 else _tt_mask_symmetrise(M, mask, e)
+
+
+def _tt_add_round(A, B, e, alpha=None):
+    """`T.tt_rank_reduce(T.tt_add(A, B), e)`, or with alpha `T.tt_rank_reduce(T.tt_add(A, T.tt_scale(alpha, B)), e)`"""
+    if alpha is None:
+        res = _fused_sum([A, B], [1.0, 1.0], [False, False], e)
+        return res if res is not None else T.tt_rank_reduce(T.tt_add(A, B), eps=e)
+    res = _fused_sum([A, B], [1.0, _f32(alpha)], [False, False], e, draws=(len(B),))
+    return res if res is not None else T.tt_rank_reduce(T.tt_add(A, T.tt_scale(alpha, B)), e)
 
 
 def _tt_copy(tt):
@@ -888,13 +935,13 @@ def _tt_ipm_newton_step(lhs, rhs, mask, X, Z, Tt, ZX, TX, st, solver):
             DXc = _tt_symmetrise(T.tt_reshape(_tt_get_block(1, Dc), (2, 2)), st.eps)
             DZc = _tt_symmetrise(T.tt_reshape(_tt_get_block(2, Dc), (2, 2)), st.eps)
             DYc = T.tt_rank_reduce(_tt_get_block(0, Dc), eps=st.eps)
-            DX = T.tt_rank_reduce(T.tt_add(DXc, DX), eps=st.eps)
-            DY = T.tt_rank_reduce(T.tt_add(DYc, DY), eps=st.eps)
-            DZ = T.tt_rank_reduce(T.tt_add(DZc, DZ), eps=st.eps)
+            DX = _tt_add_round(DXc, DX, st.eps)
+            DY = _tt_add_round(DYc, DY, st.eps)
+            DZ = _tt_add_round(DZc, DZ, st.eps)
             if st.ineq_status is IneqStatus.ACTIVE:
                 DTc = T.tt_rank_reduce(_tt_get_block(3, Dc), eps=st.eps)
                 DTc = T.tt_fast_hadamard(mask, T.tt_reshape(DTc, (2, 2)), st.eps)
-                DT = T.tt_rank_reduce(T.tt_add(DTc, DT), eps=st.eps)
+                DT = _tt_add_round(DTc, DT, st.eps)
             xs, zs = _tt_get_step_sizes(X, Z, Tt, DX, DZ, DT, mask, st)
         else:
             st.sigma = 0
@@ -1046,21 +1093,21 @@ def tt_ipm(lag_maps, obj_tt, lin_op_tt, bias_tt, ineq_mask=None, max_iter=100, m
             e_p = 0.1 * st.eta * st.primal_error_normalisation
             e_d = 0.1 * st.eta * st.dual_error_normalisation
             if fin <= 1:
-                X = _tt_symmetrise(T.tt_add(X, T.tt_scale(xs, DX)), e_p)
+                X = _tt_step_symmetrise(X, xs, DX, e_p)
             else:
-                X = _tt_psd_symmetrise(T.tt_add(X, T.tt_scale(xs, DX)), e_p)
+                X = _tt_step_symmetrise(X, xs, DX, e_p, 1)
             if fin <= 1:
-                Z = _tt_symmetrise(T.tt_add(Z, T.tt_scale(zs, DZ)), e_d)
+                Z = _tt_step_symmetrise(Z, zs, DZ, e_d)
             else:
-                Z = _tt_psd_symmetrise(T.tt_add(Z, T.tt_scale(zs, DZ)), e_d)
-            Y = T.tt_rank_reduce(T.tt_add(Y, T.tt_scale(zs, DY)), st.eps)
+                Z = _tt_step_symmetrise(Z, zs, DZ, e_d, 1)
+            Y = _tt_add_round(Y, DY, st.eps, zs)
             Y = T.tt_reshape(_tt_symmetrise(T.tt_reshape(T.tt_sub(Y, T.tt_fast_matrix_vec_mul(st.lag_map_y, Y, st.eps)),
                                                          (2, 2)), e_d), (4,))
             if st.ineq_status is IneqStatus.ACTIVE:
                 if fin <= 1:
-                    Tt = _tt_symmetrise(T.tt_add(Tt, T.tt_scale(zs, DT)), e_d)
+                    Tt = _tt_step_symmetrise(Tt, zs, DT, e_d)
                 else:
-                    Tt = _tt_mask_symmetrise(T.tt_add(Tt, T.tt_scale(zs, DT)), mask, e_d)
+                    Tt = _tt_step_symmetrise(Tt, zs, DT, e_d, 2, mask)
             elif st.ineq_status is IneqStatus.SETTING_INACTIVE:
                 solver = solver_eq
                 lhs = skel.get_submatrix(2, 2)

@@ -19,6 +19,7 @@ import os
 import numpy as np
 from . import dev as D
 from . import rng as _rng
+from ._lib import SumTerm
 
 def _const(name, arr):
     """Small constant cores, uploaded once per host thread (on that thread's stream)."""
@@ -428,9 +429,8 @@ def _tail_rank_reduce(tt, eps):
     return tt, pow(tail, 1.0 / (2 * d))
 
 
-def tt_psd_rank_reduce(tt, eps=1e-18):
-    """`cy_src/tt_ops_cy.pyx:261-325`"""
-    tt, factor = _tail_rank_reduce(tt, eps)
+def _psd_correct(tt, factor):
+    """the tracked rounding's correction, `factor` x I added (`cy_src/tt_ops_cy.pyx:311-325`)"""
     if factor is None:
         return tt
     n = tt[0].shape[1]
@@ -438,12 +438,143 @@ def tt_psd_rank_reduce(tt, eps=1e-18):
     return tt_add(tt, [eye] * len(tt))
 
 
-def tt_mask_rank_reduce(tt, mask, eps=1e-18):
-    """`cy_src/tt_ops_cy.pyx:328-388`"""
-    tt, factor = _tail_rank_reduce(tt, eps)
+def _mask_correct(tt, mask, factor):
+    """the tracked rounding's correction, `factor` x mask added (`cy_src/tt_ops_cy.pyx:376-388`)"""
     if factor is None:
         return tt
     return tt_add(tt, [D.scaled(c, factor) for c in mask])
+
+
+def tt_psd_rank_reduce(tt, eps=1e-18):
+    """`cy_src/tt_ops_cy.pyx:261-325`"""
+    return _psd_correct(*_tail_rank_reduce(tt, eps))
+
+
+def tt_mask_rank_reduce(tt, mask, eps=1e-18):
+    """`cy_src/tt_ops_cy.pyx:328-388`"""
+    tt, factor = _tail_rank_reduce(tt, eps)
+    return _mask_correct(tt, mask, factor)
+
+
+# ------------------------------------------------------------------ rounding a weighted sum of trains
+# round(sum_j c_j op_j(T_j)), op_j the identity or `tt_transpose`: the operand of the solve's
+# `tt_rank_reduce(tt_add(a, tt_scale(alpha, b)))`, `tt_sub`, `tt_sum` and `_tt_symmetrise`
+# (`src/tt_ops.py:321-328`, `src/tt_ipm.py:477-485`, `:612-640`).  These functions draw nothing from the
+# random stream and take each weight as given: a caller that mirrors `tt_scale` passes
+# float(np.float32(alpha)).
+SUM_ROUND_ONE = os.environ.get("TTIPM_SUM_ROUND_ONE", "0") == "1"
+SUM_TERMS = 4  # terms `ttk_sum_round_one` takes
+
+
+def _sum_norm(trains, coeffs, transposed):
+    n = len(trains)
+    coeffs = [1.0] * n if coeffs is None else [float(c) for c in coeffs]
+    transposed = [False] * n if transposed is None else [bool(t) for t in transposed]
+    assert n >= 1 and len(coeffs) == n and len(transposed) == n and all(len(t) == len(trains[0]) for t in trains)
+    assert all(c.dim() == 4 for t, tr in zip(trains, transposed) if tr for c in t), "a transposed term has matrix cores"
+    return coeffs, transposed
+
+
+def _sum_composed(trains, coeffs, transposed):
+    """The sum as a train of its own: `tt_transpose` where asked, core 0 times the weight (`D.scaled`, skipped
+    for a weight of 1), `tt_add` folded left to right.  A fresh list; a single unscaled term keeps its cores."""
+    terms = []
+    for t, c, tr in zip(trains, coeffs, transposed):
+        t = tt_transpose(t) if tr else list(t)
+        if c != 1.0:
+            t[0] = D.scaled(t[0], c)
+        terms.append(t)
+    return reduce(tt_add, terms)
+
+
+def _sum_round_one_plan(trains, coeffs, transposed):
+    """The arguments of `ttk_sum_round_one` for these terms -- (d, inner, rows, n, terms), the summed and the
+    bound ranks, the sum's middle extents, and what keeps the tables alive -- or None when the sum does not
+    fit one workgroup's LDS, has more than SUM_TERMS terms or a single core."""
+    d, n = len(trains[0]), len(trains)
+    if d < 2 or n > SUM_TERMS:
+        return None
+    mids = [tuple(c.shape[1:-1])[::-1] if transposed[0] else tuple(c.shape[1:-1]) for c in trains[0]]
+    I64, P, vp = ctypes.c_int64, ctypes.c_void_p * d, ctypes.c_void_p
+    inner = (I64 * d)(*[int(np.prod(m)) for m in mids])
+    rows = (I64 * d)(*[int(m[0]) for m in mids]) if any(transposed) else None
+    keep = [[D.contig(c) for c in t] for t in trains]  # the contiguous inputs stay alive until the call is enqueued
+    ptrs = [P(*[c.data_ptr() for c in t]) for t in keep]
+    ranks = [(I64 * (d + 1))(*([t[0].shape[0]] + [c.shape[-1] for c in t])) for t in trains]
+    terms = (SumTerm * n)(*[SumTerm(ctypes.cast(p, vp), ctypes.cast(r, vp), c, int(tr))
+                            for p, r, c, tr in zip(ptrs, ranks, coeffs, transposed)])
+    sums, bound = (I64 * (d + 1))(), (I64 * (d + 1))()
+    if D.lib.ttk_sum_round_one_lds(d, inner, n, terms, sums, bound) < 0:
+        return None
+    return (d, inner, rows, n, terms), list(sums), list(bound), mids, (keep, ptrs, ranks)
+
+
+def sum_round_one_lds(trains, transposed=None):
+    """Bytes of LDS `ttk_sum_round_one` needs for the sum of these trains (`transposed`: one flag per train),
+    -1 if it does not fit one workgroup or has more than SUM_TERMS terms (the sum is then built and rounded)."""
+    coeffs, transposed = _sum_norm(trains, None, transposed)
+    plan = _sum_round_one_plan(trains, coeffs, transposed)
+    if plan is None:
+        return -1
+    d, inner, _, n, terms = plan[0]
+    return int(D.lib.ttk_sum_round_one_lds(d, inner, n, terms, None, None))
+
+
+def _sum_round_one(plan, eps, mode):
+    """`ttk_sum_round_one`: `_round_one` on the sum, whose cores exist only inside the kernel's two loads.  One
+    launch into one fresh buffer sized by the bound ranks, one host read (the ranks and the tail).  Returns
+    (tt, tail factor or None); the caller's tensors are never written."""
+    (d, inner, rows, n, terms), sums, bound, mids, keep = plan
+    assert bound == retraction_ranks(inner, sums, [1 << 62] * (d - 1)), bound
+    outs, _ = _packed_out(keep[0][0], bound, inner)
+    P = ctypes.c_void_p * d
+    info = D.empty(d + 2)
+    D._stream()
+    D.check(D.lib.ttk_sum_round_one(D.ctx(), d, inner, rows, n, terms, float(eps), mode,
+                                    P(*[o.data_ptr() for o in outs]), info.data_ptr()), "sum_round_one")
+    got = D.read(info)
+    q = [int(v) for v in got[:d + 1]]
+    tt = [o[:q[k] * inner[k] * q[k + 1]].view(q[k], *mids[k], q[k + 1]) for k, o in enumerate(outs)]
+    return tt, (pow(float(got[d + 1]), 1.0 / (2 * d)) if mode else None)
+
+
+def _sum_native(trains, coeffs, transposed, eps, mode):
+    """(tt, tail factor or None) from `ttk_sum_round_one`, or None where that path is not taken: the switch is
+    off, there is no GPU, the sum does not fit, or the existing functions return the input as it is (d = 1, a
+    single term with every rank 1)."""
+    if not (SUM_ROUND_ONE and D.DEV.type == "cuda") or len(trains[0]) < 2:
+        return None
+    if len(trains) == 1 and all(r == 1 for r in tt_ranks(trains[0])):
+        return None
+    plan = _sum_round_one_plan(trains, coeffs, transposed)
+    return None if plan is None else _sum_round_one(plan, eps, mode)
+
+
+def tt_sum_rank_reduce(trains, coeffs=None, transposed=None, eps=1e-18):
+    """`tt_rank_reduce` of sum_j coeffs[j] op_j(trains[j]), op_j = `tt_transpose` where transposed[j].  With
+    TTIPM_SUM_ROUND_ONE=1, on the GPU, for at most SUM_TERMS terms whose sum fits (`sum_round_one_lds`): one
+    launch and one host read (`ttk_sum_round_one`), the sum never built.  Otherwise the sum is built
+    (`_sum_composed`) and rounded as today.  Off by default, like TTIPM_ROUND_ONE."""
+    coeffs, transposed = _sum_norm(trains, coeffs, transposed)
+    res = _sum_native(trains, coeffs, transposed, eps, 0)
+    return res[0] if res is not None else tt_rank_reduce(_sum_composed(trains, coeffs, transposed), eps)
+
+
+def _sum_tail_rank_reduce(trains, coeffs, transposed, eps):
+    coeffs, transposed = _sum_norm(trains, coeffs, transposed)
+    res = _sum_native(trains, coeffs, transposed, eps, 1)
+    return res if res is not None else _tail_rank_reduce(_sum_composed(trains, coeffs, transposed), eps)
+
+
+def tt_sum_psd_rank_reduce(trains, coeffs=None, transposed=None, eps=1e-18):
+    """`tt_psd_rank_reduce` of the sum (see `tt_sum_rank_reduce`)"""
+    return _psd_correct(*_sum_tail_rank_reduce(trains, coeffs, transposed, eps))
+
+
+def tt_sum_mask_rank_reduce(trains, coeffs=None, transposed=None, mask=None, eps=1e-18):
+    """`tt_mask_rank_reduce` of the sum (see `tt_sum_rank_reduce`)"""
+    tt, factor = _sum_tail_rank_reduce(trains, coeffs, transposed, eps)
+    return _mask_correct(tt, mask, factor)
 
 
 def retraction_ranks(inner, ranks, upper):

@@ -13,6 +13,15 @@ a device synchronise, per call; the table gives the median over the rounds and t
 the launches and host waits per call and what was computed (ranks, distance from the input).
 
     python tools/bench_round.py one [reps] [rounds]
+
+`sum` times the rounding of a weighted sum of trains, by the same method (host clock around `reps` calls ending
+in a synchronise, the paths alternating round by round, median and min / max over the rounds, wrapper and read
+included), at d = 10 with cores (r,2,2,R): a + alpha b at term ranks 4+4 and 6+6, and the symmetrised update
+0.5 ((X + xs DX) + (X + xs DX)^T) at term ranks 3+3 (summed rank 12) and 6+6 (24).  Three paths in one run:
+today's composition (`tt_scale` + `tt_add` (+ `tt_transpose`) + `ttk_round`), the same materialised sum into
+`ttk_round_one`, and the fused `ttk_sum_round_one`, which never builds the sum.
+
+    python tools/bench_round.py sum [reps] [rounds]
 """
 import hashlib
 import os
@@ -124,8 +133,88 @@ def main_one(argv):
             bench_one(10, r, eps_rel, tracked, reps, rounds)
 
 
+def bench_sum(d, r, symmetrise, reps, rounds):
+    rng = np.random.default_rng(5)
+    ranks = [1] + [r] * (d - 1) + [1]
+    A, B = train(rng, ranks), train(rng, ranks)
+    alpha = 0.37
+    w = float(np.float32(alpha))
+    if symmetrise:
+        terms, coeffs, flags = [A, B, A, B], [0.5, 0.5 * w, 0.5, 0.5 * w], [False, False, True, True]
+    else:
+        terms, coeffs, flags = [A, B], [1.0, w], [False, False]
+    lds = T.sum_round_one_lds(terms, flags)
+    assert lds >= 0
+    eps = 1e-2 * T.tt_norm(A)
+
+    def composed(one):
+        def f():
+            T.ROUND_ONE, T.SUM_ROUND_ONE = one, False
+            M = T.tt_add(A, T.tt_scale(alpha, B))
+            if symmetrise:
+                M = T.tt_scale(0.5, T.tt_add(M, T.tt_transpose(M)))
+            return T.tt_rank_reduce(M, eps)
+        return f
+
+    def fused():
+        T.ROUND_ONE, T.SUM_ROUND_ONE = False, True
+        return T.tt_sum_rank_reduce(terms, coeffs, flags, eps)
+
+    what = (("composed + ttk_round (the default)", composed(False)), ("composed + ttk_round_one", composed(True)),
+            ("ttk_sum_round_one", fused))
+    info = {}
+    ref = None
+    for name, f in what:
+        out = f()
+        torch.cuda.synchronize()
+        l0, s0 = D.lib.ttk_launch_count(), D.lib.ttk_sync_count()
+        f()
+        torch.cuda.synchronize()
+        nl, ns = D.lib.ttk_launch_count() - l0, D.lib.ttk_sync_count() - s0
+        dense = T.tt_to_tensor(out)
+        ref = dense if ref is None else ref
+        info[name] = (T.tt_ranks(out), nl, ns, float(np.linalg.norm(dense - ref) / np.linalg.norm(ref)))
+        for _ in range(20):  # warm-up of every shape the timed window uses
+            f()
+    torch.cuda.synchronize()
+    times = {name: [] for name, _ in what}
+    for _ in range(rounds):
+        for name, f in what:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                f()
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) / reps * 1e6)
+    T.ROUND_ONE = T.SUM_ROUND_ONE = False
+    kind = "symmetrised update, 4 terms" if symmetrise else "a + alpha b, 2 terms"
+    print(f"d={d} {kind}, term ranks {r}+{r} (summed {len(terms) * r}), cores (r,2,2,R), eps {eps:g}; LDS {lds} bytes; "
+          f"{reps} calls x {rounds} rounds, us per call", flush=True)
+    for name, _ in what:
+        t = np.array(times[name])
+        rk, nl, ns, err = info[name]
+        print(f"{name:36s} median {np.median(t):8.1f}  min {t.min():8.1f}  max {t.max():8.1f}  launches {nl:3d}  "
+              f"host waits {ns:2d}  |out - default|/|default| {err:.2e}  ranks {rk}", flush=True)
+    _, mat, new = (np.array(times[name]) for name, _ in what)
+    spread = max(mat.max() - mat.min(), new.max() - new.min())
+    gap = float(np.median(mat) - np.median(new))
+    print(f"ttk_sum_round_one: {np.median(mat) / np.median(new):.2f}x composed + ttk_round_one (medians {gap:.1f} us "
+          f"apart, min-max spread {spread:.1f} us: {'beyond' if abs(gap) > spread else 'within'} the spread)\n",
+          flush=True)
+
+
+def main_sum(argv):
+    reps = int(argv[0]) if argv else 100
+    rounds = int(argv[1]) if len(argv) > 1 else 7
+    assert torch.cuda.is_available(), "bench_round needs an MI355X"
+    for r, symmetrise in ((4, False), (6, False), (3, True), (6, True)):
+        bench_sum(10, r, symmetrise, reps, rounds)
+
+
 if __name__ == "__main__":
     if sys.argv[1:2] == ["one"]:
         main_one(sys.argv[2:])
+    elif sys.argv[1:2] == ["sum"]:
+        main_sum(sys.argv[2:])
     else:
         main()
