@@ -654,6 +654,39 @@ int64_t ttk_sum_round_one_lds(int d, const int64_t *inner, int nterms, const ttk
 int ttk_sum_round_one(ttk_ctx ctx, int d, const int64_t *inner, const int64_t *rows, int nterms,
                       const ttk_sum_term *terms, double eps, int mode, double *const *out, double *info);
 
+/* ttk_round_one on the core-wise product of two trains that is never built: the operand of the device path's
+ * `tt_fast_matrix_vec_mul`, `tt_fast_mat_mat_mul` and `tt_fast_hadamard` (cy_src/tt_ops_cy.pyx:391-502 as
+ * DESIGN.md §3.1 computes them: the exact Kronecker-bond product, rounded once at eps), i.e. ttk_zipup's
+ * result by another route.  kind and modes[3k..3k+2] are ttk_zipup's (an entry the kind does not use is
+ * ignored).  The product P has the bond ranks R_k = a_ranks[k] b_ranks[k]; its core k is row-major
+ * (R_k, mid_k, R_{k+1}) with row index a rb_k + b and column index A rb_{k+1} + B, ttk_zipup's layout:
+ *   kind 0  a (ra, m, n, Ra), b (rb, n, Rb)      mid = m,   index i        sum_n a[a,i,n,A] b[b,n,B]
+ *   kind 1  a (ra, m, k, Ra), b (rb, k, n, Rb)   mid = m n, index i n + j  sum_k a[a,i,k,A] b[b,k,j,B]
+ *   kind 2  a (ra, i, Ra),    b (rb, i, Rb)      mid = i                   a[a,i,A] b[b,i,B]
+ *   kind 3  a (ra, i, j, Ra), b (rb, i, j, Rb)   mid = i j, index i j' + j a[a,i,j,A] b[b,i,j,B]
+ * The kernel's two loads write these cores straight into LDS, every element once by the thread that owns
+ * it, from the factors' cores in global memory; they never exist in global memory.  The arithmetic is
+ * fixed: the first term is one rounded product, every further term is added by fma with the contracted
+ * index ascending, so two calls give the same bits and a Hadamard element is the IEEE product.  The factors
+ * may alias each other (x o x); the inputs are read only.  Everything after the loads is ttk_round_one on
+ * P: the plan (LDS bytes, thread count, bound ranks) is ttk_round_one_lds(d, mid, R), the same rank rule,
+ * eps, mode, out and info, one launch, no host read, and the bits of ttk_round_one on a materialised P that
+ * holds the same numbers.
+ * a[k], b[k]: device pointers to the contiguous fp64 cores above; a_ranks, b_ranks: d+1 entries each, the
+ * boundary ranks 1.  out[k]: bound[k] mid_k bound[k+1] doubles that overlap no input; info: d + 2 doubles.
+ * ttk_prod_round_one_lds: the bytes of LDS, or -1 when the product does not fit one workgroup (at most
+ * 160 KiB and 32 cores; a rank, an extent or a product of two above the LDS capacity) or the arguments are
+ * invalid -- the caller then takes ttk_zipup; it fills prod_ranks and bound (d+1 entries each) unless
+ * NULL.  ttk_prod_round_one validates on the host (kind in 0 .. 3; d >= 2; no null array, table or core;
+ * every rank and used extent >= 1; the boundary ranks of both factors 1; eps finite and >= 0; mode 0 or 1;
+ * out, every out[k] and info non-null; the LDS fit) and returns TTK_ERR_ARG without launching when a check
+ * fails. */
+int64_t ttk_prod_round_one_lds(int kind, int d, const int64_t *a_ranks, const int64_t *b_ranks,
+                               const int64_t *modes, int64_t *prod_ranks, int64_t *bound);
+int ttk_prod_round_one(ttk_ctx ctx, int kind, int d, const double *const *a, const int64_t *a_ranks,
+                       const double *const *b, const int64_t *b_ranks, const int64_t *modes,
+                       double eps, int mode, double *const *out, double *info);
+
 /* Dense Schur-complement local KKT solve in one call (SURVEY §8(b) `ttk_local_assemble` +
  * `ttk_dense_schur_solve`; the dense branch of `_ipm_local_solver`, src/tt_ipm.py:183-229):
  * assembles L_XI = B22 diag(inv_I), L_eq = B01, L_Z = B21 (each 'lsr,smnS,LSR->lmLrnR'), Cholesky of

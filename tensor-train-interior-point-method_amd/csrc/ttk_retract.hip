@@ -42,6 +42,12 @@
 // that owns it (rt_load_core).  The plan is the one of the summed ranks; everything after the loads is
 // retract_kernel<true, RtPlan>'s code.
 //
+// `ttk_prod_round_one` is `ttk_round_one` on the core-wise product of two trains (`tt_fast_matrix_vec_mul`,
+// `tt_fast_mat_mat_mul`, `tt_fast_hadamard` as the device path computes them, DESIGN.md §3.1: Kronecker bonds,
+// rounded once at eps) that is never built either: the same two loads write core k of the product, row a r_b + b,
+// column A R_b + B, each element one multiply or a short fma chain over the contracted index of two small cores
+// read from global memory.  The plan is the one of the product ranks.
+//
 // LDS holds one step's working set, not the train: two carried-core regions that the phases use in
 // turn (QR input / Q, then Z / the Jacobi's rows), one core from global memory or scratch, the
 // rotations G, M and a few small vectors.  The products are VALU fma chains, as in the siblings.
@@ -84,6 +90,20 @@ struct RtSumArg {
   const double *core[RS_TERMS][TT_MAXD];
 };
 static_assert(sizeof(RtSumArg) < 4096, "the plan and the terms travel as one kernel argument");
+
+// `ttk_prod_round_one`: the plan of the product train (p.r = ra rb, p.n the product's middle extents, p.core
+// unused) and the two factors.  Core k of a is (ra_k, m0_k, m1_k, ra_{k+1}); of b (rb_k, m1_k, m2_k, rb_{k+1})
+// where the products contract m1 (kind 0 with m2 = 1, kind 1), (rb_k, m0_k m1_k, rb_{k+1}) where they multiply
+// elementwise (kind 2 with m1 = 1, kind 3).  An extent the kind does not use is stored as 1.
+struct RtProdArg {
+  RtPlan p;
+  int kind;
+  int ra[TT_MAXD + 1], rb[TT_MAXD + 1];        // the factors' bond ranks
+  int m0[TT_MAXD], m1[TT_MAXD], m2[TT_MAXD];   // the physical extents of core k
+  const double *a[TT_MAXD];
+  const double *b[TT_MAXD];
+};
+static_assert(sizeof(RtProdArg) < 4096, "the plan and the factors travel as one kernel argument");
 
 // Validates the extents, applies the rank rule and lays out LDS and scratch.  Returns the bytes of
 // dynamic LDS, -1 when the train does not fit one workgroup (or has more than TT_MAXD cores), -2 on
@@ -176,6 +196,7 @@ __device__ int rt_kept_rank(const double *sv, const int *perm, int pp, double th
 
 __device__ __forceinline__ const RtPlan &rt_plan_of(const RtPlan &a) { return a; }
 __device__ __forceinline__ const RtPlan &rt_plan_of(const RtSumArg &a) { return a.p; }
+__device__ __forceinline__ const RtPlan &rt_plan_of(const RtProdArg &a) { return a.p; }
 
 // Core k of the train, (r_k, n_k, r_{k+1}) row-major, into dst.  No barrier: the caller's next one publishes it.
 __device__ __forceinline__ void rt_load_core(double *dst, const RtPlan &a, int k) {
@@ -211,9 +232,40 @@ __device__ __forceinline__ void rt_load_core(double *dst, const RtSumArg &s, int
   }
 }
 
+// Core k of the product train: element (a rb + b, mid, A Rb + B) from the factors' cores in global memory.
+// Kinds 0 and 1: mid = i m2 + j, sum over c < m1 of a[a, i, c, A] b[b, c, j, B], the first term a rounded
+// product, the others added by fma with c ascending.  Kinds 2 and 3: a[a, mid, A] b[b, mid, B], one rounded
+// product.  Each destination element is written once, by the thread that owns it; the largest source index is
+// below the factor core's size, which the plan's fit keeps under 2^31 (ra m0 Ra and rb m2 Rb <= TT_CAP each,
+// m1 <= TT_CAP).  kind and every extent are uniform across the workgroup.
+__device__ __forceinline__ void rt_load_core(double *dst, const RtProdArg &s, int k) {
+  const int rb = s.rb[k], Ra = s.ra[k + 1], Rb = s.rb[k + 1];
+  const int m0 = s.m0[k], m1 = s.m1[k], m2 = s.m2[k];
+  const int n = s.p.n[k], R1 = s.p.r[k + 1], nR1 = n * R1, total = s.p.r[k] * nR1;
+  const double *__restrict__ pa = s.a[k], *__restrict__ pb = s.b[k];
+  const bool contract = s.kind < 2;
+  for (int e = threadIdx.x; e < total; e += blockDim.x) {
+    const int row = e / nR1, rem = e - row * nR1, mid = rem / R1, col = rem - mid * R1;
+    const int a = row / rb, b = row - a * rb, A = col / Rb, B = col - A * Rb;
+    double v;
+    if (contract) {
+      const int i = mid / m2, j = mid - i * m2;
+      const double *xa = pa + ((a * m0 + i) * m1) * Ra + A;  // stride Ra over c
+      const double *xb = pb + (b * m1 * m2 + j) * Rb + B;    // stride m2 Rb over c
+      const int sb = m2 * Rb;
+      v = __dmul_rn(xa[0], xb[0]);
+      for (int c = 1; c < m1; ++c) v = fma(xa[c * Ra], xb[c * sb], v);
+    } else {
+      v = __dmul_rn(pa[(a * n + mid) * Ra + A], pb[(b * n + mid) * Rb + B]);
+    }
+    dst[e] = v;
+  }
+}
+
 // ADAPT false: `ttk_retract`, every q_i from the plan.  ADAPT true: `ttk_round_one`, p.q holds the bounds and
 // q_{i+1} is decided after bond i's Jacobi.  Arg: RtPlan, the cores as they lie in global memory, or RtSumArg,
-// the cores of the summed train (`ttk_sum_round_one`); it only enters the two rt_load_core calls.
+// the cores of the summed train (`ttk_sum_round_one`), or RtProdArg, the cores of the product train
+// (`ttk_prod_round_one`); it only enters the two rt_load_core calls.
 template <bool ADAPT, class Arg>
 __global__ __launch_bounds__(1024) void retract_kernel(const Arg arg, double *scr) {
   const RtPlan &p = rt_plan_of(arg);
@@ -332,6 +384,41 @@ int64_t rs_plan(int d, const int64_t *inner, int nterms, const ttk_sum_term *ter
     for (int k = 0; k < d; ++k) a->core[j][k] = on ? terms[j].cores[k] : nullptr;
   }
   for (int k = 0; k < d; ++k) a->n1[k] = (int)inner[k], a->p.core[k] = nullptr;
+  return shm;
+}
+
+// `ttk_prod_round_one`'s checks on the factors and the plan of the product train: the bytes of dynamic LDS, -1
+// when the product does not fit one workgroup, -2 on invalid arguments.  prod: the product ranks, d + 1 entries.
+int64_t rp_plan(int kind, int d, const int64_t *a_ranks, const int64_t *b_ranks, const int64_t *modes, RtProdArg *a,
+                int64_t *words, int64_t *prod) {
+  if (kind < 0 || kind > 3 || d < 2 || !a_ranks || !b_ranks || !modes) return -2;
+  const bool use1 = kind != 2, use2 = kind == 1;  // whether modes[3k + 1], modes[3k + 2] mean anything
+  bool big = d > TT_MAXD;
+  for (int k = 0; k <= d; ++k) {
+    if (a_ranks[k] < 1 || b_ranks[k] < 1) return -2;
+    big |= a_ranks[k] > TT_CAP || b_ranks[k] > TT_CAP || a_ranks[k] * b_ranks[k] > TT_CAP;  // factors <= TT_CAP first
+  }
+  for (int k = 0; k < d; ++k) {
+    const int64_t m0 = modes[3 * k], m1 = use1 ? modes[3 * k + 1] : 1, m2 = use2 ? modes[3 * k + 2] : 1;
+    if (m0 < 1 || m1 < 1 || m2 < 1) return -2;
+    big |= m0 > TT_CAP || m1 > TT_CAP || m2 > TT_CAP || m0 * (kind == 1 ? m2 : kind == 3 ? m1 : 1) > TT_CAP;
+  }
+  if (a_ranks[0] != 1 || a_ranks[d] != 1 || b_ranks[0] != 1 || b_ranks[d] != 1) return -2;
+  if (big) return -1;  // d <= TT_MAXD, every rank, extent and product of two <= TT_CAP from here on
+  int64_t inner[TT_MAXD];
+  for (int k = 0; k < d; ++k) {
+    const int64_t m0 = modes[3 * k], m1 = use1 ? modes[3 * k + 1] : 1, m2 = use2 ? modes[3 * k + 2] : 1;
+    inner[k] = kind == 1 ? m0 * m2 : kind == 3 ? m0 * m1 : m0;
+    a->m0[k] = (int)m0, a->m1[k] = (int)m1, a->m2[k] = (int)m2;
+  }
+  for (int k = 0; k <= d; ++k) {
+    prod[k] = a_ranks[k] * b_ranks[k];
+    a->ra[k] = (int)a_ranks[k], a->rb[k] = (int)b_ranks[k];
+  }
+  const int64_t shm = rt_plan(d, inner, prod, nullptr, true, &a->p, words);
+  if (shm < 0) return shm;
+  a->kind = kind;
+  for (int k = 0; k < d; ++k) a->a[k] = a->b[k] = a->p.core[k] = nullptr;
   return shm;
 }
 
@@ -464,6 +551,52 @@ int ttk_sum_round_one(ttk_ctx ctx, int d, const int64_t *inner, const int64_t *r
   TTK_HIP(w.alloc(words));
   tt_lds_attr(retract_kernel<true, RtSumArg>, shm);
   hipLaunchKernelGGL((retract_kernel<true, RtSumArg>), dim3(1), dim3(a.p.nt), (size_t)shm, w.st, a, w.get());
+  TTK_LAUNCH_CHECK();
+  return TTK_OK;
+}
+
+int64_t ttk_prod_round_one_lds(int kind, int d, const int64_t *a_ranks, const int64_t *b_ranks, const int64_t *modes,
+                               int64_t *prod_ranks, int64_t *bound) {
+  RtProdArg a;
+  int64_t words, prod[TT_MAXD + 1];
+  const int64_t b = rp_plan(kind, d, a_ranks, b_ranks, modes, &a, &words, prod);
+  if (b < 0) return -1;
+  for (int k = 0; prod_ranks && k <= d; ++k) prod_ranks[k] = prod[k];
+  for (int k = 0; bound && k <= d; ++k) bound[k] = a.p.q[k];
+  return b;
+}
+
+int ttk_prod_round_one(ttk_ctx ctx, int kind, int d, const double *const *a, const int64_t *a_ranks,
+                       const double *const *b, const int64_t *b_ranks, const int64_t *modes, double eps, int mode,
+                       double *const *out, double *info) {
+  ttk::CtxScope scope(ctx);
+  RtProdArg g;
+  int64_t words = 0, prod[TT_MAXD + 1];
+  const bool ok = a && b && out && info && eps >= 0.0 && eps <= 1.79769313486231570e308 && (mode == 0 || mode == 1);
+  const int64_t shm = ok ? rp_plan(kind, d, a_ranks, b_ranks, modes, &g, &words, prod) : -2;
+  if (const int e = tt_plan_status(
+          shm,
+          "ttk_prod_round_one: bad arguments (kind 0 to 3, d >= 2, every rank and extent >= 1, boundary ranks 1, no "
+          "null pointer, eps finite and >= 0, mode 0 or 1)",
+          "ttk_prod_round_one: the product does not fit one workgroup's LDS (ttk_prod_round_one_lds)"))
+    return e;
+  for (int k = 0; k < d; ++k) {
+    if (!a[k] || !b[k] || !out[k]) {
+      ttk::set_error("ttk_prod_round_one: null core %d", k);
+      return TTK_ERR_ARG;
+    }
+    g.a[k] = a[k];
+    g.b[k] = b[k];
+    g.p.out[k] = out[k];
+  }
+  const double e = (mode ? eps / 2.0 : eps) / std::sqrt((double)(d - 1));
+  g.p.thr2 = e * e;
+  g.p.track = mode;
+  g.p.info = info;
+  TtScratch w(ttk::ctx().stream);  // the orthogonalised cores 1 .. d-1
+  TTK_HIP(w.alloc(words));
+  tt_lds_attr(retract_kernel<true, RtProdArg>, shm);
+  hipLaunchKernelGGL((retract_kernel<true, RtProdArg>), dim3(1), dim3(g.p.nt), (size_t)shm, w.st, g, w.get());
   TTK_LAUNCH_CHECK();
   return TTK_OK;
 }

@@ -608,13 +608,18 @@ def _tt_extents(*trains):
     return (inner,) + tuple((I64 * (d + 1))(*([t[0].shape[0]] + [c.shape[-1] for c in t])) for t in trains)
 
 
-def _packed_out(tt, rk, inner):
-    """One fresh buffer for the output cores of ranks `rk`: its flat slices, one per core (what a native
-    call writes), and their views (rk[k], *middle extents of tt[k], rk[k+1])."""
-    sizes = [rk[k] * inner[k] * rk[k + 1] for k in range(len(tt))]
+def _packed_flat(rk, inner):
+    """One fresh buffer for the output cores of ranks `rk` and middle extents `inner`: its flat slices, one per
+    core (what a native call writes)."""
+    sizes = [rk[k] * inner[k] * rk[k + 1] for k in range(len(inner))]
     offs = np.concatenate(([0], np.cumsum([(s + 1) & ~1 for s in sizes])))  # 16-byte aligned cores
     buf = D.empty(int(offs[-1]))
-    outs = [buf[int(o):int(o) + s] for o, s in zip(offs, sizes)]
+    return [buf[int(o):int(o) + s] for o, s in zip(offs, sizes)]
+
+
+def _packed_out(tt, rk, inner):
+    """`_packed_flat`'s slices and their views (rk[k], *middle extents of tt[k], rk[k+1])."""
+    outs = _packed_flat(rk, inner)
     return outs, [o.view(rk[k], *tt[k].shape[1:-1], rk[k + 1]) for k, o in enumerate(outs)]
 
 
@@ -999,13 +1004,8 @@ def _kron_round(cores, eps):
 NATIVE_ZIPUP = os.environ.get("TTIPM_NATIVE_ZIPUP", "1") == "1"
 
 
-def _native_zipup(kind, a, b, eps, out_modes):
-    """`ttk_zipup` (one library call: the core-wise products into fresh buffers + one in-place
-    rounding; the same einsum plans and rounding launches as the Python composition below, so
-    bit-identical to it).  out_modes[k]: the product core's physical shape."""
-    d = len(a)
-    ar = [a[0].shape[0]] + [c.shape[-1] for c in a]
-    br = [b[0].shape[0]] + [c.shape[-1] for c in b]
+def _zipup_modes(kind, a, b):
+    """`ttk_zipup`'s modes: three physical extents per core, 1 where the kind has none"""
     mids = []
     for x, y in zip(a, b):
         if kind == 0:
@@ -1016,6 +1016,17 @@ def _native_zipup(kind, a, b, eps, out_modes):
             mids += [x.shape[1], 1, 1]
         else:
             mids += [x.shape[1], x.shape[2], 1]
+    return mids
+
+
+def _native_zipup(kind, a, b, eps, out_modes):
+    """`ttk_zipup` (one library call: the core-wise products into fresh buffers + one in-place
+    rounding; the same einsum plans and rounding launches as the Python composition below, so
+    bit-identical to it).  out_modes[k]: the product core's physical shape."""
+    d = len(a)
+    ar = [a[0].shape[0]] + [c.shape[-1] for c in a]
+    br = [b[0].shape[0]] + [c.shape[-1] for c in b]
+    mids = _zipup_modes(kind, a, b)
     inner = [int(np.prod(m)) for m in out_modes]
     outs = [D.empty(ar[k] * br[k] * inner[k] * ar[k + 1] * br[k + 1]) for k in range(d)]
     ca = [D.contig(c) for c in a]
@@ -1035,11 +1046,92 @@ def _use_native_zipup():
     return NATIVE_ZIPUP and NATIVE_ROUND and D.DEV.type == "cuda"
 
 
+# ------------------------------------------------------------------ rounding a product of two trains
+# The products above write d Kronecker-bond cores and round them with 2(d-1) factorisation launches and one
+# host read per bond.  `ttk_prod_round_one` forms the product core inside the one-launch rounding's two loads
+# (kind and modes are `ttk_zipup`'s): one launch, one host read, the product never in global memory.  Off by
+# default, like TTIPM_ROUND_ONE and TTIPM_SUM_ROUND_ONE.  Nothing here draws from the random stream.
+PROD_ROUND_ONE = os.environ.get("TTIPM_PROD_ROUND_ONE", "0") == "1"
+
+
+def _prod_out_modes(kind, a, b):
+    """the middle shape of every product core"""
+    if kind == 0:
+        return [(x.shape[1],) for x in a]
+    if kind == 1:
+        return [(x.shape[1], y.shape[2]) for x, y in zip(a, b)]
+    return [tuple(x.shape[1:-1]) for x in a]
+
+
+def _prod_round_one_plan(kind, a, b):
+    """The arguments of `ttk_prod_round_one` for a (x), (.) or (o) b -- (kind, d, a, a_ranks, b, b_ranks, modes),
+    the product and the bound ranks, the product's middle extents, and what keeps the tables alive -- or None
+    when the product does not fit one workgroup's LDS or has a single core."""
+    d = len(a)
+    if d < 2 or len(b) != d:
+        return None
+    I64, P = ctypes.c_int64, ctypes.c_void_p * d
+    ar = (I64 * (d + 1))(*([a[0].shape[0]] + [c.shape[-1] for c in a]))
+    br = (I64 * (d + 1))(*([b[0].shape[0]] + [c.shape[-1] for c in b]))
+    modes = (I64 * (3 * d))(*_zipup_modes(kind, a, b))
+    prod, bound = (I64 * (d + 1))(), (I64 * (d + 1))()
+    if D.lib.ttk_prod_round_one_lds(kind, d, ar, br, modes, prod, bound) < 0:
+        return None
+    keep = ([D.contig(c) for c in a], [D.contig(c) for c in b])  # alive until the call is enqueued
+    pa, pb = (P(*[c.data_ptr() for c in t]) for t in keep)
+    return (kind, d, pa, ar, pb, br, modes), list(prod), list(bound), (keep, pa, pb)
+
+
+def prod_round_one_lds(kind, a, b):
+    """Bytes of LDS `ttk_prod_round_one` needs for the product of these trains (kind: `ttk_zipup`'s, 0 matrix x
+    vector, 1 matrix x matrix, 2 / 3 Hadamard of vector / matrix trains), -1 if it does not fit one workgroup
+    (`ttk_zipup` then runs)."""
+    plan = _prod_round_one_plan(kind, a, b)
+    if plan is None:
+        return -1
+    kind, d, _, ar, _, br, modes = plan[0]
+    return int(D.lib.ttk_prod_round_one_lds(kind, d, ar, br, modes, None, None))
+
+
+def _prod_round_one(plan, out_modes, eps, mode):
+    """`ttk_prod_round_one`: `_round_one` on the product, whose cores exist only inside the kernel's two loads.
+    One launch into one fresh buffer sized by the bound ranks, one host read (the ranks and the tail).  Returns
+    (tt, tail factor or None); the caller's tensors are never written."""
+    (kind, d, pa, ar, pb, br, modes), prod, bound, keep = plan
+    inner = [int(np.prod(m)) for m in out_modes]
+    assert bound == retraction_ranks(inner, prod, [1 << 62] * (d - 1)), bound
+    outs = _packed_flat(bound, inner)
+    info = D.empty(d + 2)
+    D._stream()
+    D.check(D.lib.ttk_prod_round_one(D.ctx(), kind, d, pa, ar, pb, br, modes, float(eps), mode,
+                                     (ctypes.c_void_p * d)(*[o.data_ptr() for o in outs]), info.data_ptr()),
+            "prod_round_one")
+    got = D.read(info)
+    q = [int(v) for v in got[:d + 1]]
+    tt = [o[:q[k] * inner[k] * q[k + 1]].view(q[k], *out_modes[k], q[k + 1]) for k, o in enumerate(outs)]
+    return tt, (pow(float(got[d + 1]), 1.0 / (2 * d)) if mode else None)
+
+
+def _prod_native(kind, a, b, eps):
+    """The rounded product from `ttk_prod_round_one`, or None where that path is not taken: the switch is off,
+    there is no GPU, eps <= 0 or d = 1 (the product is returned unrounded), every product rank is 1 (nothing
+    to round), or the product does not fit."""
+    if not (PROD_ROUND_ONE and D.DEV.type == "cuda") or len(a) < 2 or not eps > 0:
+        return None
+    if all(x.shape[-1] * y.shape[-1] == 1 for x, y in zip(a[:-1], b[:-1])):
+        return None
+    plan = _prod_round_one_plan(kind, a, b)
+    return None if plan is None else _prod_round_one(plan, _prod_out_modes(kind, a, b), eps, 0)[0]
+
+
 def tt_fast_matrix_vec_mul(mat, vec, eps=1e-18):
     """`cy_src/tt_ops_cy.pyx:428-447`: mat (r_A,m,n,R_A) x vec (r,n,R) -> (r_A r, m, R_A R), rounded
     at eps (see the note above)."""
     if ZIPUP:
         return _zipup_matrix_vec_mul(mat, vec, eps)
+    res = _prod_native(0, mat, vec, eps)
+    if res is not None:
+        return res
     if _use_native_zipup():
         return _native_zipup(0, mat, vec, eps, [(a.shape[1],) for a in mat])
     cores = []
@@ -1054,6 +1146,9 @@ def tt_fast_mat_mat_mul(m1, m2, eps=1e-18):
     """`cy_src/tt_ops_cy.pyx:449-464`: core-wise matrix product, rounded at eps."""
     if ZIPUP:
         return _zipup_mat_mat_mul(m1, m2, eps)
+    res = _prod_native(1, m1, m2, eps)
+    if res is not None:
+        return res
     if _use_native_zipup():
         return _native_zipup(1, m1, m2, eps, [(a.shape[1], b.shape[2]) for a, b in zip(m1, m2)])
     cores = []
@@ -1069,6 +1164,9 @@ def tt_fast_hadamard(t1, t2, eps=1e-18):
     if ZIPUP:
         return _zipup_hadamard(t1, t2, eps)
     four = t1[0].dim() == 4 and t2[0].dim() == 4
+    res = _prod_native(3 if four else 2, t1, t2, eps) if four or (t1[0].dim() == 3 and t2[0].dim() == 3) else None
+    if res is not None:
+        return res
     if _use_native_zipup() and (four or (t1[0].dim() == 3 and t2[0].dim() == 3)):
         return _native_zipup(3 if four else 2, t1, t2, eps, [tuple(a.shape[1:-1]) for a in t1])
     cores = []

@@ -22,6 +22,15 @@ today's composition (`tt_scale` + `tt_add` (+ `tt_transpose`) + `ttk_round`), th
 `ttk_round_one`, and the fused `ttk_sum_round_one`, which never builds the sum.
 
     python tools/bench_round.py sum [reps] [rounds]
+
+`prod` times the rounding of a product of two trains, by the same method, at d = 10: the matrix product of two
+trains of cores (r,2,2,R) at ranks 3 x 3 and 4 x 4, an operator of cores (2,4,4,2) applied to a vector train of
+ranks 4 and 6, and the Hadamard product of a rank-8 matrix train with a rank-1 mask, each at eps = 1e-2 of the
+product's norm.  Three paths in one run: today's default (`ttk_zipup`: the product cores written, then
+`ttk_round`), the same materialised product into `ttk_round_one`, and the fused `ttk_prod_round_one`, which
+never builds the product.
+
+    python tools/bench_round.py prod [reps] [rounds]
 """
 import hashlib
 import os
@@ -211,8 +220,92 @@ def main_sum(argv):
         bench_sum(10, r, symmetrise, reps, rounds)
 
 
+def bench_prod(kind, d, ra, rb, reps, rounds):
+    rng = np.random.default_rng(5)
+
+    def cores(r, mid):
+        rk = [1] + [r] * (d - 1) + [1]
+        return [D.from_numpy(rng.standard_normal((rk[k], *mid, rk[k + 1])) * (0.5 ** np.arange(rk[k + 1])))
+                for k in range(d)]
+
+    if kind == 0:
+        A, B, what_is = cores(ra, (4, 4)), cores(rb, (4,)), "operator (r,4,4,R) x vector (r,4,R)"
+    else:
+        A, B = cores(ra, (2, 2)), cores(rb, (2, 2))
+        what_is = "matrix product of (r,2,2,R) trains" if kind == 1 else "Hadamard product of (r,2,2,R) trains"
+    fn = (T.tt_fast_matrix_vec_mul, T.tt_fast_mat_mat_mul, None, T.tt_fast_hadamard)[kind]
+    lds = T.prod_round_one_lds(kind, A, B)
+    assert lds >= 0
+    T.ROUND_ONE = T.PROD_ROUND_ONE = False
+    eps = 1e-2 * T.tt_norm(fn(A, B, 0.0))
+
+    def default():
+        T.ROUND_ONE = T.PROD_ROUND_ONE = False
+        return fn(A, B, eps)
+
+    def materialised():
+        T.ROUND_ONE, T.PROD_ROUND_ONE = True, False
+        return T.tt_rank_reduce(fn(A, B, 0.0), eps)
+
+    def fused():
+        T.ROUND_ONE, T.PROD_ROUND_ONE = False, True
+        return fn(A, B, eps)
+
+    what = (("ttk_zipup (the default)", default), ("product + ttk_round_one", materialised),
+            ("ttk_prod_round_one", fused))
+    info = {}
+    ref = None
+    for name, f in what:
+        out = f()
+        torch.cuda.synchronize()
+        l0, s0 = D.lib.ttk_launch_count(), D.lib.ttk_sync_count()
+        f()
+        torch.cuda.synchronize()
+        nl, ns = D.lib.ttk_launch_count() - l0, D.lib.ttk_sync_count() - s0
+        dense = T.tt_to_tensor(out)
+        ref = dense if ref is None else ref
+        info[name] = (T.tt_ranks(out), nl, ns, float(np.linalg.norm(dense - ref) / np.linalg.norm(ref)))
+        for _ in range(20):  # warm-up of every shape the timed window uses
+            f()
+    torch.cuda.synchronize()
+    times = {name: [] for name, _ in what}
+    for _ in range(rounds):
+        for name, f in what:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                f()
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) / reps * 1e6)
+    T.ROUND_ONE = T.PROD_ROUND_ONE = False
+    print(f"d={d} {what_is}, ranks {ra} x {rb} (product {ra * rb}), eps {eps:g}; LDS {lds} bytes; "
+          f"{reps} calls x {rounds} rounds, us per call", flush=True)
+    for name, _ in what:
+        t = np.array(times[name])
+        rk, nl, ns, err = info[name]
+        print(f"{name:26s} median {np.median(t):8.1f}  min {t.min():8.1f}  max {t.max():8.1f}  launches {nl:3d}  "
+              f"host waits {ns:2d}  |out - default|/|default| {err:.2e}  ranks {rk}", flush=True)
+    old, mat, new = (np.array(times[name]) for name, _ in what)
+    for other, t in (("ttk_zipup", old), ("product + ttk_round_one", mat)):
+        spread = max(t.max() - t.min(), new.max() - new.min())
+        gap = float(np.median(t) - np.median(new))
+        print(f"ttk_prod_round_one: {np.median(t) / np.median(new):.2f}x {other} (medians {gap:.1f} us apart, min-max "
+              f"spread {spread:.1f} us: {'beyond' if abs(gap) > spread else 'within'} the spread)", flush=True)
+    print(flush=True)
+
+
+def main_prod(argv):
+    reps = int(argv[0]) if argv else 100
+    rounds = int(argv[1]) if len(argv) > 1 else 7
+    assert torch.cuda.is_available(), "bench_round needs an MI355X"
+    for kind, ra, rb in ((1, 3, 3), (1, 4, 4), (0, 2, 4), (0, 2, 6), (3, 8, 1)):
+        bench_prod(kind, 10, ra, rb, reps, rounds)
+
+
 if __name__ == "__main__":
-    if sys.argv[1:2] == ["one"]:
+    if sys.argv[1:2] == ["prod"]:
+        main_prod(sys.argv[2:])
+    elif sys.argv[1:2] == ["one"]:
         main_one(sys.argv[2:])
     elif sys.argv[1:2] == ["sum"]:
         main_sum(sys.argv[2:])
