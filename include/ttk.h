@@ -687,6 +687,53 @@ int ttk_prod_round_one(ttk_ctx ctx, int kind, int d, const double *const *a, con
                        const double *const *b, const int64_t *b_ranks, const int64_t *modes,
                        double eps, int mode, double *const *out, double *info);
 
+/* ttk_round_one on S = sum_{j < nterms} coef_j op_j(T_j), 1 <= nterms <= 4, that is never built: each T_j is a
+ * plain train (kind -1: a, a_ranks; b, b_ranks and modes NULL) or the core-wise product of two trains (kind
+ * 0 .. 3: ttk_prod_round_one's operand of a and b, in its layout, row a rb_k + b, column A rb_{k+1} + B, the
+ * middle index of the table above), and op_j is the identity or the swap of the two middle indices as in
+ * ttk_sum_round_one.  This is the operand of the solve's residuals round(L vec(X) - b),
+ * round(Ladj Y - Z - C), of the symmetrised Y update and of round(bv mask + mask o X); a sum of plain terms and
+ * a single product are special cases.
+ * inner[k] is S's middle extent; every term's own middle extent must equal it (kind 0: m; kind 1: m n; kind
+ * 2: i; kind 3: i j; a plain term: its cores are (a_ranks[k], inner[k], a_ranks[k+1])).  rows[k] = n1_k with
+ * n2_k = inner[k] / n1_k: a transposed term's own core k has the middle extents (n2_k, n1_k) row-major, and
+ * element (a, i1 n2 + i2, b) of op_j(T_j) is the term's (a, i2 n1 + i1, b) -- for a product term the middle
+ * index is remapped first and the product element is computed at the remapped index.  rows may be NULL when
+ * no term is transposed.
+ * Layout: S has tt_add's, with the term ranks R_j[k] = a_ranks[k] (plain) or a_ranks[k] b_ranks[k] (product):
+ * core 0 holds the terms side by side, core d-1 stacked, an interior core block diagonal at the prefix sums
+ * of R_j in term order, everything else exactly 0.0.
+ * Arithmetic: each LDS element is written once by the thread that owns it.  A plain element is loaded; a
+ * product element is ttk_prod_round_one's (kinds 2, 3: one rounded multiply; kinds 0, 1: the rounded
+ * product at c = 0, then fma with c ascending); coef_j multiplies the finished element of core 0 once,
+ * rounded, and a coef of exactly 1.0 copies the bits.  Hence the bits of ttk_sum_round_one for plain terms
+ * only, of ttk_prod_round_one for one untransposed product with coef 1.0, and of ttk_round_one on a
+ * materialised S that holds the same numbers.  Everything after the loads is ttk_round_one on S: the plan is
+ * ttk_round_one_lds(d, inner, sum_ranks), the same rank rule, eps, mode and out.
+ * info: d + 3 doubles.  info[0 .. d] the ranks, info[d+1] the discarded tail (mode 1, else 0.0), as
+ * ttk_round_one; info[d+2] = ||result||^2, the sum of squares of the last output core (the others have
+ * orthonormal columns), reduced in a fixed order, so two calls give the same bits.
+ * Limits: at most 4 terms, at most 2 of them products, at most 32 cores, every rank, extent and product of
+ * two at most the LDS capacity in doubles (they travel as 16-bit entries of one kernel argument under 4 KB).
+ * ttk_affine_round_one_lds: the bytes of LDS, or -1 when S does not fit one workgroup, passes a limit or the
+ * arguments are invalid -- the caller then builds the products and the sum and rounds them; it fills
+ * sum_ranks and bound (d+1 entries each) unless NULL.  ttk_affine_round_one validates on the host (every check
+ * of ttk_sum_round_one and ttk_prod_round_one per term; kind in -1 .. 3; b, b_ranks and modes NULL exactly for
+ * kind -1; a product's middle extent equal to inner[k]; rows given if a term is transposed, rows[k] dividing
+ * inner[k]; the limits; the LDS fit) and returns TTK_ERR_ARG without launching when a check fails. */
+typedef struct {
+  int kind;                 /* -1: the train a;  0..3: ttk_zipup's product of a and b */
+  int transpose;            /* 0 or 1 */
+  double coef;              /* finite */
+  const double *const *a;  const int64_t *a_ranks;
+  const double *const *b;  const int64_t *b_ranks;   /* NULL, NULL for kind -1 */
+  const int64_t *modes;     /* ttk_zipup's 3 per core; NULL for kind -1 */
+} ttk_affine_term;
+int64_t ttk_affine_round_one_lds(int d, const int64_t *inner, int nterms, const ttk_affine_term *terms,
+                                 int64_t *sum_ranks, int64_t *bound);
+int ttk_affine_round_one(ttk_ctx ctx, int d, const int64_t *inner, const int64_t *rows, int nterms,
+                         const ttk_affine_term *terms, double eps, int mode, double *const *out, double *info);
+
 /* Dense Schur-complement local KKT solve in one call (SURVEY §8(b) `ttk_local_assemble` +
  * `ttk_dense_schur_solve`; the dense branch of `_ipm_local_solver`, src/tt_ipm.py:183-229):
  * assembles L_XI = B22 diag(inv_I), L_eq = B01, L_Z = B21 (each 'lsr,smnS,LSR->lmLrnR'), Cholesky of

@@ -95,6 +95,8 @@ _SIGS = {
     "ttk_sum_round_one": (i32, [vp, i32, vp, vp, i32, vp, f64, i32, vp, vp]),
     "ttk_prod_round_one_lds": (i64, [i32, i32, vp, vp, vp, vp, vp]),
     "ttk_prod_round_one": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, f64, i32, vp, vp]),
+    "ttk_affine_round_one_lds": (i64, [i32, vp, i32, vp, vp, vp]),
+    "ttk_affine_round_one": (i32, [vp, i32, vp, vp, i32, vp, f64, i32, vp, vp]),
     "ttk_dense_schur_solve": (i32, [vp, i64, i64, i64, vp, vp, vp, vp, vp]),
     "ttk_dense_schur_solve_ineq": (i32, [vp, i64, i64, i64, vp, vp, vp, vp]),
     "ttk_fused_set_mfma": (i32, [i32]),
@@ -165,6 +167,12 @@ TTK_OK, TTK_ERR_ARG, TTK_ERR_HIP, TTK_ERR_NOT_PD, TTK_ERR_SINGULAR, TTK_ERR_NOT_
 class SumTerm(ctypes.Structure):
     """`ttk_sum_term` (include/ttk.h): one term of `ttk_sum_round_one`"""
     _fields_ = [("cores", vp), ("ranks", vp), ("coef", f64), ("transpose", i32)]
+
+
+class AffineTerm(ctypes.Structure):
+    """`ttk_affine_term` (include/ttk.h): one term of `ttk_affine_round_one`"""
+    _fields_ = [("kind", i32), ("transpose", i32), ("coef", f64), ("a", vp), ("a_ranks", vp), ("b", vp),
+                ("b_ranks", vp), ("modes", vp)]
 
 
 class TTKError(RuntimeError):

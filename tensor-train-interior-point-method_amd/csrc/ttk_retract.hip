@@ -48,6 +48,13 @@
 // column A R_b + B, each element one multiply or a short fma chain over the contracted index of two small cores
 // read from global memory.  The plan is the one of the product ranks.
 //
+// `ttk_affine_round_one` closes the family: S = sum_j c_j op_j(T_j) of up to RS_TERMS terms, each a plain train
+// or the core-wise product of two (at most RA_PRODS of them), in `tt_add`'s block layout at the prefix sums of
+// the term ranks.  Its loader finds the owning term as the sum's does and computes the element with the
+// functions the two loaders above share, so a sum of plain terms or a single product gives their bits.  It
+// alone also leaves ||result||^2 in info[d + 2]: after phase B every output core but the last has orthonormal
+// columns, so that is the sum of squares of the last carried core, reduced by wave 0 in a fixed order.
+//
 // LDS holds one step's working set, not the train: two carried-core regions that the phases use in
 // turn (QR input / Q, then Z / the Jacobi's rows), one core from global memory or scratch, the
 // rotations G, M and a few small vectors.  The products are VALU fma chains, as in the siblings.
@@ -104,6 +111,26 @@ struct RtProdArg {
   const double *b[TT_MAXD];
 };
 static_assert(sizeof(RtProdArg) < 4096, "the plan and the factors travel as one kernel argument");
+
+constexpr int RA_PRODS = 2;  // product terms of an affine operand
+
+// `ttk_affine_round_one`: the plan of S (p.r the summed ranks, p.core unused) and the terms.  Term j is the train
+// a[j] (kind -1) or the product of a[j] and b[slot[j]] (kinds 0 .. 3, RtProdArg's extents per slot).  Ranks and
+// extents are 16-bit (TT_CAP fits) so that four terms, two of them products, travel as one kernel argument.
+struct RtAffineArg {
+  RtPlan p;
+  int nterms;
+  signed char kind[RS_TERMS], slot[RS_TERMS], tr[RS_TERMS];
+  double coef[RS_TERMS];                      // applied to the term's core 0
+  unsigned short n1[TT_MAXD];                 // first middle extent of S's core k
+  unsigned short r[RS_TERMS][TT_MAXD + 1];    // the terms' bond ranks in S (ra rb for a product)
+  unsigned short ra[RA_PRODS][TT_MAXD + 1], rb[RA_PRODS][TT_MAXD + 1];
+  unsigned short m0[RA_PRODS][TT_MAXD], m1[RA_PRODS][TT_MAXD], m2[RA_PRODS][TT_MAXD];
+  const double *a[RS_TERMS][TT_MAXD];
+  const double *b[RA_PRODS][TT_MAXD];
+};
+static_assert(TT_CAP < 65536, "ranks and extents are stored as 16-bit");
+static_assert(sizeof(RtAffineArg) < 4096, "the plan and the terms travel as one kernel argument");
 
 // Validates the extents, applies the rank rule and lays out LDS and scratch.  Returns the bytes of
 // dynamic LDS, -1 when the train does not fit one workgroup (or has more than TT_MAXD cores), -2 on
@@ -197,10 +224,44 @@ __device__ int rt_kept_rank(const double *sv, const int *perm, int pp, double th
 __device__ __forceinline__ const RtPlan &rt_plan_of(const RtPlan &a) { return a; }
 __device__ __forceinline__ const RtPlan &rt_plan_of(const RtSumArg &a) { return a.p; }
 __device__ __forceinline__ const RtPlan &rt_plan_of(const RtProdArg &a) { return a.p; }
+__device__ __forceinline__ const RtPlan &rt_plan_of(const RtAffineArg &a) { return a.p; }
 
 // Core k of the train, (r_k, n_k, r_{k+1}) row-major, into dst.  No barrier: the caller's next one publishes it.
 __device__ __forceinline__ void rt_load_core(double *dst, const RtPlan &a, int k) {
   ro_load(dst, a.core[k], a.r[k] * a.n[k] * a.r[k + 1]);
+}
+
+// The element code the operand loaders share, so that equal operands give equal bits.
+// The term's own middle index of S's middle index i = i1 n2 + i2: i2 n1 + i1 where the term is transposed.
+__device__ __forceinline__ int rt_term_mid(bool tr, int i, int n1, int n2) {
+  if (!tr) return i;
+  const int i1 = i / n2, i2 = i - i1 * n2;
+  return i2 * n1 + i1;
+}
+
+// The weight, applied in core 0 only; a weight of exactly 1.0 copies the bits.
+__device__ __forceinline__ double rt_weighted(bool first, double coef, double x) {
+  return (first && coef != 1.0) ? __dmul_rn(coef, x) : x;
+}
+
+// Element (a rb + b, mid, A Rb + B) of a product core from the factors' cores in global memory.  Kinds 0 and
+// 1: mid = i m2 + j, sum over c < m1 of a[a, i, c, A] b[b, c, j, B], the first term a rounded product, the
+// others added by fma with c ascending.  Kinds 2 and 3: a[a, mid, A] b[b, mid, B], one rounded product, n the
+// product's middle extent.  The largest source index is below the factor core's size, which the plan's fit
+// keeps under 2^31 (ra m0 Ra and rb m2 Rb <= TT_CAP each, m1 <= TT_CAP).
+__device__ __forceinline__ double rt_prod_elem(bool contract, const double *__restrict__ pa,
+                                               const double *__restrict__ pb, int a, int b, int mid, int A, int B,
+                                               int Ra, int Rb, int m0, int m1, int m2, int n) {
+  if (contract) {
+    const int i = mid / m2, j = mid - i * m2;
+    const double *xa = pa + ((a * m0 + i) * m1) * Ra + A;  // stride Ra over c
+    const double *xb = pb + (b * m1 * m2 + j) * Rb + B;    // stride m2 Rb over c
+    const int sb = m2 * Rb;
+    double v = __dmul_rn(xa[0], xb[0]);
+    for (int c = 1; c < m1; ++c) v = fma(xa[c * Ra], xb[c * sb], v);
+    return v;
+  }
+  return __dmul_rn(pa[(a * n + mid) * Ra + A], pb[(b * n + mid) * Rb + B]);
 }
 
 // Core k of the summed train: element (a, i, b) belongs to the one term whose row range holds a (every term
@@ -218,13 +279,8 @@ __device__ __forceinline__ void rt_load_core(double *dst, const RtSumArg &s, int
       const int ra = s.r[j][k], rb = s.r[j][k + 1];
       const int la = first ? 0 : a - A, lb = last ? 0 : b - B;
       if (la >= 0 && la < ra && lb >= 0 && lb < rb) {
-        int mid = i;
-        if (s.tr[j]) {
-          const int i1 = i / n2, i2 = i - i1 * n2;
-          mid = i2 * n1 + i1;
-        }
-        const double x = s.core[j][k][(la * n + mid) * rb + lb];
-        v = (first && s.coef[j] != 1.0) ? __dmul_rn(s.coef[j], x) : x;
+        const int mid = rt_term_mid(s.tr[j] != 0, i, n1, n2);
+        v = rt_weighted(first, s.coef[j], s.core[j][k][(la * n + mid) * rb + lb]);
       }
       A += ra, B += rb;
     }
@@ -232,12 +288,8 @@ __device__ __forceinline__ void rt_load_core(double *dst, const RtSumArg &s, int
   }
 }
 
-// Core k of the product train: element (a rb + b, mid, A Rb + B) from the factors' cores in global memory.
-// Kinds 0 and 1: mid = i m2 + j, sum over c < m1 of a[a, i, c, A] b[b, c, j, B], the first term a rounded
-// product, the others added by fma with c ascending.  Kinds 2 and 3: a[a, mid, A] b[b, mid, B], one rounded
-// product.  Each destination element is written once, by the thread that owns it; the largest source index is
-// below the factor core's size, which the plan's fit keeps under 2^31 (ra m0 Ra and rb m2 Rb <= TT_CAP each,
-// m1 <= TT_CAP).  kind and every extent are uniform across the workgroup.
+// Core k of the product train: element (a rb + b, mid, A Rb + B) by rt_prod_elem.  Each destination element is
+// written once, by the thread that owns it.  kind and every extent are uniform across the workgroup.
 __device__ __forceinline__ void rt_load_core(double *dst, const RtProdArg &s, int k) {
   const int rb = s.rb[k], Ra = s.ra[k + 1], Rb = s.rb[k + 1];
   const int m0 = s.m0[k], m1 = s.m1[k], m2 = s.m2[k];
@@ -247,25 +299,54 @@ __device__ __forceinline__ void rt_load_core(double *dst, const RtProdArg &s, in
   for (int e = threadIdx.x; e < total; e += blockDim.x) {
     const int row = e / nR1, rem = e - row * nR1, mid = rem / R1, col = rem - mid * R1;
     const int a = row / rb, b = row - a * rb, A = col / Rb, B = col - A * Rb;
-    double v;
-    if (contract) {
-      const int i = mid / m2, j = mid - i * m2;
-      const double *xa = pa + ((a * m0 + i) * m1) * Ra + A;  // stride Ra over c
-      const double *xb = pb + (b * m1 * m2 + j) * Rb + B;    // stride m2 Rb over c
-      const int sb = m2 * Rb;
-      v = __dmul_rn(xa[0], xb[0]);
-      for (int c = 1; c < m1; ++c) v = fma(xa[c * Ra], xb[c * sb], v);
-    } else {
-      v = __dmul_rn(pa[(a * n + mid) * Ra + A], pb[(b * n + mid) * Rb + B]);
+    dst[e] = rt_prod_elem(contract, pa, pb, a, b, mid, A, B, Ra, Rb, m0, m1, m2, n);
+  }
+}
+
+// Core k of the affine operand: the owning term as in the sum's loader, the term's middle index remapped first
+// where it is transposed, then the plain element loaded or the product element computed at that index, then
+// the weight.  Each destination element is written once, by the thread that owns it; the term tables are
+// kernel arguments indexed by the uniform j and k.
+__device__ __forceinline__ void rt_load_core(double *dst, const RtAffineArg &s, int k) {
+  const int n = s.p.n[k], R1 = s.p.r[k + 1], nR1 = n * R1, total = s.p.r[k] * nR1;
+  const int n1 = s.n1[k], n2 = n / n1;
+  const bool first = k == 0, last = k == s.p.d - 1;
+  for (int e = threadIdx.x; e < total; e += blockDim.x) {
+    const int row = e / nR1, rem = e - row * nR1, i = rem / R1, col = rem - i * R1;
+    double v = 0.0;
+    int A0 = 0, B0 = 0;
+    for (int j = 0; j < s.nterms; ++j) {
+      const int rj = s.r[j][k], Rj = s.r[j][k + 1];
+      const int la = first ? 0 : row - A0, lb = last ? 0 : col - B0;
+      if (la >= 0 && la < rj && lb >= 0 && lb < Rj) {
+        const int mid = rt_term_mid(s.tr[j] != 0, i, n1, n2);
+        double x;
+        if (s.kind[j] < 0) {
+          x = s.a[j][k][(la * n + mid) * Rj + lb];
+        } else {
+          const int t = s.slot[j], rb = s.rb[t][k], Rb = s.rb[t][k + 1];
+          const int a = la / rb, b = la - a * rb, A = lb / Rb, B = lb - A * Rb;
+          x = rt_prod_elem(s.kind[j] < 2, s.a[j][k], s.b[t][k], a, b, mid, A, B, s.ra[t][k + 1], Rb, s.m0[t][k],
+                           s.m1[t][k], s.m2[t][k], n);
+        }
+        v = rt_weighted(first, s.coef[j], x);
+      }
+      A0 += rj, B0 += Rj;
     }
     dst[e] = v;
   }
 }
 
+// Whether the operand's kernel leaves the squared norm of the result in info[d + 2]: a compile-time property
+// of the argument type, so the other instantiations keep their code.
+template <class Arg> struct RtNorm2 { static constexpr bool value = false; };
+template <> struct RtNorm2<RtAffineArg> { static constexpr bool value = true; };
+
 // ADAPT false: `ttk_retract`, every q_i from the plan.  ADAPT true: `ttk_round_one`, p.q holds the bounds and
 // q_{i+1} is decided after bond i's Jacobi.  Arg: RtPlan, the cores as they lie in global memory, or RtSumArg,
 // the cores of the summed train (`ttk_sum_round_one`), or RtProdArg, the cores of the product train
-// (`ttk_prod_round_one`); it only enters the two rt_load_core calls.
+// (`ttk_prod_round_one`), or RtAffineArg, the cores of a weighted sum of trains and products
+// (`ttk_affine_round_one`); it only enters the two rt_load_core calls and, for RtAffineArg, adds info[d + 2].
 template <bool ADAPT, class Arg>
 __global__ __launch_bounds__(1024) void retract_kernel(const Arg arg, double *scr) {
   const RtPlan &p = rt_plan_of(arg);
@@ -349,6 +430,17 @@ __global__ __launch_bounds__(1024) void retract_kernel(const Arg arg, double *sc
     p.info[d] = 1.0;
     p.info[d + 1] = tail;
   }
+  if (RtNorm2<Arg>::value) {
+    // ||result||^2 = the sum of squares of the last carried core (published by the loop's last barrier): wave 0
+    // alone, lane l the elements l, l + 64, ... ascending, then the fixed wave tree
+    if (threadIdx.x < 64) {
+      const int cnt = qi * p.n[d - 1];
+      double part = 0.0;
+      for (int e = threadIdx.x; e < cnt; e += 64) part = fma(Z[e], Z[e], part);
+      part = ttk::wave_sum(part);
+      if (threadIdx.x == 0) p.info[d + 2] = part;
+    }
+  }
 }
 
 // `ttk_sum_round_one`'s checks on the terms and the plan of the summed train: the bytes of dynamic LDS, -1 when
@@ -387,10 +479,11 @@ int64_t rs_plan(int d, const int64_t *inner, int nterms, const ttk_sum_term *ter
   return shm;
 }
 
-// `ttk_prod_round_one`'s checks on the factors and the plan of the product train: the bytes of dynamic LDS, -1
-// when the product does not fit one workgroup, -2 on invalid arguments.  prod: the product ranks, d + 1 entries.
-int64_t rp_plan(int kind, int d, const int64_t *a_ranks, const int64_t *b_ranks, const int64_t *modes, RtProdArg *a,
-                int64_t *words, int64_t *prod) {
+// The checks on the two factors of a product that `ttk_prod_round_one` and `ttk_affine_round_one` share: -2 on
+// invalid arguments, -1 when a rank, an extent or a product of two passes TT_CAP or d passes TT_MAXD, else 0
+// with inner[k] the product's middle extents and m[3k ..] the physical extents (1 where the kind has none).
+int rp_check(int kind, int d, const int64_t *a_ranks, const int64_t *b_ranks, const int64_t *modes, int64_t *inner,
+             int *m) {
   if (kind < 0 || kind > 3 || d < 2 || !a_ranks || !b_ranks || !modes) return -2;
   const bool use1 = kind != 2, use2 = kind == 1;  // whether modes[3k + 1], modes[3k + 2] mean anything
   bool big = d > TT_MAXD;
@@ -405,12 +498,22 @@ int64_t rp_plan(int kind, int d, const int64_t *a_ranks, const int64_t *b_ranks,
   }
   if (a_ranks[0] != 1 || a_ranks[d] != 1 || b_ranks[0] != 1 || b_ranks[d] != 1) return -2;
   if (big) return -1;  // d <= TT_MAXD, every rank, extent and product of two <= TT_CAP from here on
-  int64_t inner[TT_MAXD];
   for (int k = 0; k < d; ++k) {
     const int64_t m0 = modes[3 * k], m1 = use1 ? modes[3 * k + 1] : 1, m2 = use2 ? modes[3 * k + 2] : 1;
     inner[k] = kind == 1 ? m0 * m2 : kind == 3 ? m0 * m1 : m0;
-    a->m0[k] = (int)m0, a->m1[k] = (int)m1, a->m2[k] = (int)m2;
+    m[3 * k] = (int)m0, m[3 * k + 1] = (int)m1, m[3 * k + 2] = (int)m2;
   }
+  return 0;
+}
+
+// `ttk_prod_round_one`'s checks on the factors and the plan of the product train: the bytes of dynamic LDS, -1
+// when the product does not fit one workgroup, -2 on invalid arguments.  prod: the product ranks, d + 1 entries.
+int64_t rp_plan(int kind, int d, const int64_t *a_ranks, const int64_t *b_ranks, const int64_t *modes, RtProdArg *a,
+                int64_t *words, int64_t *prod) {
+  int64_t inner[TT_MAXD];
+  int m[3 * TT_MAXD];
+  if (const int chk = rp_check(kind, d, a_ranks, b_ranks, modes, inner, m)) return chk;
+  for (int k = 0; k < d; ++k) a->m0[k] = m[3 * k], a->m1[k] = m[3 * k + 1], a->m2[k] = m[3 * k + 2];
   for (int k = 0; k <= d; ++k) {
     prod[k] = a_ranks[k] * b_ranks[k];
     a->ra[k] = (int)a_ranks[k], a->rb[k] = (int)b_ranks[k];
@@ -419,6 +522,83 @@ int64_t rp_plan(int kind, int d, const int64_t *a_ranks, const int64_t *b_ranks,
   if (shm < 0) return shm;
   a->kind = kind;
   for (int k = 0; k < d; ++k) a->a[k] = a->b[k] = a->p.core[k] = nullptr;
+  return shm;
+}
+
+// `ttk_affine_round_one`'s checks on the terms and the plan of S: the bytes of dynamic LDS, -1 when S does not fit
+// one workgroup, -2 on invalid arguments or more than RS_TERMS terms or RA_PRODS products.  sum: the summed
+// ranks, d + 1 entries.
+int64_t ra_plan(int d, const int64_t *inner, int nterms, const ttk_affine_term *terms, RtAffineArg *a,
+                int64_t *words, int64_t *sum) {
+  if (nterms < 1 || nterms > RS_TERMS || !terms) return -2;
+  if (tt_check_extents(d, inner, {}) == -2) return -2;
+  int nprod = 0;
+  for (int j = 0; j < nterms; ++j) nprod += terms[j].kind >= 0;
+  if (nprod > RA_PRODS) return -2;
+  bool big = false;
+  int64_t mid[TT_MAXD];
+  int m[RA_PRODS][3 * TT_MAXD];
+  nprod = 0;
+  for (int j = 0; j < nterms; ++j) {
+    const ttk_affine_term &t = terms[j];
+    if (t.kind < -1 || t.kind > 3 || !t.a || !t.a_ranks || !std::isfinite(t.coef) ||
+        (t.transpose != 0 && t.transpose != 1))
+      return -2;
+    if (t.kind < 0) {
+      if (t.b || t.b_ranks || t.modes) return -2;
+      const int chk = tt_check_extents(d, inner, {t.a_ranks});
+      if (chk == -2 || t.a_ranks[0] != 1 || t.a_ranks[d] != 1) return -2;
+      big |= chk != 0;
+    } else {
+      if (!t.b) return -2;
+      const int chk = rp_check(t.kind, d, t.a_ranks, t.b_ranks, t.modes, mid, m[nprod++]);
+      if (chk == -2) return -2;
+      big |= chk != 0;
+      for (int k = 0; !chk && k < d; ++k)
+        if (mid[k] != inner[k]) return -2;  // the product's middle extent is S's
+    }
+  }
+  if (big || tt_check_extents(d, inner, {}) != 0) return -1;  // d <= TT_MAXD, ranks and extents <= TT_CAP from here on
+  for (int j = 0; j < nterms; ++j)
+    for (int k = 0; k < d; ++k)
+      if (!terms[j].a[k] || (terms[j].kind >= 0 && !terms[j].b[k])) return -2;
+  sum[0] = sum[d] = 1;
+  for (int k = 1; k < d; ++k) {
+    sum[k] = 0;
+    for (int j = 0; j < nterms; ++j)
+      sum[k] += terms[j].kind < 0 ? terms[j].a_ranks[k] : terms[j].a_ranks[k] * terms[j].b_ranks[k];
+  }
+  const int64_t shm = rt_plan(d, inner, sum, nullptr, true, &a->p, words);
+  if (shm < 0) return shm;
+  a->nterms = nterms;
+  nprod = 0;
+  for (int t = 0; t < RA_PRODS; ++t)
+    for (int k = 0; k <= d; ++k) {
+      a->ra[t][k] = a->rb[t][k] = 1;
+      if (k < d) a->m0[t][k] = a->m1[t][k] = a->m2[t][k] = 1, a->b[t][k] = nullptr;
+    }
+  for (int j = 0; j < RS_TERMS; ++j) {
+    const bool on = j < nterms, prod = on && terms[j].kind >= 0;
+    const int t = prod ? nprod++ : 0;
+    a->kind[j] = on ? (signed char)terms[j].kind : -1;
+    a->slot[j] = (signed char)t;
+    a->tr[j] = on ? (signed char)terms[j].transpose : 0;
+    a->coef[j] = on ? terms[j].coef : 0.0;
+    for (int k = 0; k <= d; ++k) {
+      const int64_t ra = on ? terms[j].a_ranks[k] : 0, rb = prod ? terms[j].b_ranks[k] : 1;
+      a->r[j][k] = (unsigned short)(ra * rb);
+      if (prod) a->ra[t][k] = (unsigned short)ra, a->rb[t][k] = (unsigned short)rb;
+    }
+    for (int k = 0; k < d; ++k) {
+      a->a[j][k] = on ? terms[j].a[k] : nullptr;
+      if (prod) {
+        a->b[t][k] = terms[j].b[k];
+        a->m0[t][k] = (unsigned short)m[t][3 * k], a->m1[t][k] = (unsigned short)m[t][3 * k + 1];
+        a->m2[t][k] = (unsigned short)m[t][3 * k + 2];
+      }
+    }
+  }
+  for (int k = 0; k < d; ++k) a->n1[k] = (unsigned short)inner[k], a->p.core[k] = nullptr;
   return shm;
 }
 
@@ -597,6 +777,62 @@ int ttk_prod_round_one(ttk_ctx ctx, int kind, int d, const double *const *a, con
   TTK_HIP(w.alloc(words));
   tt_lds_attr(retract_kernel<true, RtProdArg>, shm);
   hipLaunchKernelGGL((retract_kernel<true, RtProdArg>), dim3(1), dim3(g.p.nt), (size_t)shm, w.st, g, w.get());
+  TTK_LAUNCH_CHECK();
+  return TTK_OK;
+}
+
+int64_t ttk_affine_round_one_lds(int d, const int64_t *inner, int nterms, const ttk_affine_term *terms,
+                                 int64_t *sum_ranks, int64_t *bound) {
+  RtAffineArg a;
+  int64_t words, sum[TT_MAXD + 1];
+  const int64_t b = ra_plan(d, inner, nterms, terms, &a, &words, sum);
+  if (b < 0) return -1;
+  for (int k = 0; sum_ranks && k <= d; ++k) sum_ranks[k] = sum[k];
+  for (int k = 0; bound && k <= d; ++k) bound[k] = a.p.q[k];
+  return b;
+}
+
+int ttk_affine_round_one(ttk_ctx ctx, int d, const int64_t *inner, const int64_t *rows, int nterms,
+                         const ttk_affine_term *terms, double eps, int mode, double *const *out, double *info) {
+  ttk::CtxScope scope(ctx);
+  RtAffineArg a;
+  int64_t words = 0, sum[TT_MAXD + 1];
+  const bool ok = out && info && eps >= 0.0 && eps <= 1.79769313486231570e308 && (mode == 0 || mode == 1);
+  const int64_t shm = ok ? ra_plan(d, inner, nterms, terms, &a, &words, sum) : -2;
+  if (const int e = tt_plan_status(
+          shm,
+          "ttk_affine_round_one: bad arguments (d >= 2, 1 to 4 terms, at most 2 of them products, kind -1 to 3, b, "
+          "b_ranks and modes null exactly for kind -1, every rank and extent >= 1, boundary ranks 1, a product's "
+          "middle extent equal to inner, no null pointer, coef finite, transpose 0 or 1, eps finite and >= 0, mode 0 "
+          "or 1)",
+          "ttk_affine_round_one: the operand does not fit one workgroup's LDS (ttk_affine_round_one_lds)"))
+    return e;
+  bool transposed = false;
+  for (int j = 0; j < nterms; ++j) transposed |= terms[j].transpose != 0;
+  if (transposed && !rows) {
+    ttk::set_error("ttk_affine_round_one: a transposed term needs rows");
+    return TTK_ERR_ARG;
+  }
+  for (int k = 0; k < d; ++k) {
+    if (rows && (rows[k] < 1 || inner[k] % rows[k] != 0)) {
+      ttk::set_error("ttk_affine_round_one: rows[%d] does not divide inner[%d]", k, k);
+      return TTK_ERR_ARG;
+    }
+    if (!out[k]) {
+      ttk::set_error("ttk_affine_round_one: null out %d", k);
+      return TTK_ERR_ARG;
+    }
+    if (rows) a.n1[k] = (unsigned short)rows[k];
+    a.p.out[k] = out[k];
+  }
+  const double e = (mode ? eps / 2.0 : eps) / std::sqrt((double)(d - 1));
+  a.p.thr2 = e * e;
+  a.p.track = mode;
+  a.p.info = info;
+  TtScratch w(ttk::ctx().stream);  // the orthogonalised cores 1 .. d-1
+  TTK_HIP(w.alloc(words));
+  tt_lds_attr(retract_kernel<true, RtAffineArg>, shm);
+  hipLaunchKernelGGL((retract_kernel<true, RtAffineArg>), dim3(1), dim3(a.p.nt), (size_t)shm, w.st, a, w.get());
   TTK_LAUNCH_CHECK();
   return TTK_OK;
 }

@@ -592,21 +592,91 @@ class IPMStatus:
     eta = 1e-3
 
 
+def _affine_on():
+    """whether `ttk_affine_round_one` can run at all; where it cannot, every call site below is its old expression
+    and nothing else"""
+    return T.AFFINE_ROUND_ONE and D.DEV.type == "cuda"
+
+
+def _fused_affine(terms, e, mode=0, draws=(), mids=None):
+    """(round(sum_j coef_j op_j(T_j)), ||result||^2) by `ttk_affine_round_one` (TTIPM_AFFINE_ROUND_ONE=1, on the
+    GPU, an operand that fits and keeps the term limits), else None: the caller then runs its expression as it
+    stands -- the same library calls in the same order, the same random draws.  terms and mids:
+    `T.tt_affine_rank_reduce`'s.  mode 0 / 1: `tt_rank_reduce` / the PSD variant.  draws: the lengths of the
+    trains the replaced `tt_scale` calls (`tt_sub`'s among them) would scale, in call order; the same `randint`s
+    are drawn (`cy_src/tt_ops_cy.pyx:94-114`), so the MT19937 stream stays aligned with the reference's."""
+    res = T._affine_native(terms, e, mode, mids) if _affine_on() else None
+    if res is None:
+        return None
+    for n in draws:
+        _rng.R().randint(0, n)
+    tt, factor, norm2 = res
+    return (tt if mode == 0 else T._psd_correct(tt, factor)), norm2
+
+
+def _primal_feasibility(L, b, X, st):
+    """(`tt_compute_primal_feasibility`, its squared norm where the fused call produced it, else None).  Fused
+    only where `tt_mat_vec_mul` would take its fast branch: L vec(X) - b is then rounded once at e, not twice."""
+    e = 0.01 * st.eta * st.primal_error_normalisation
+    if _affine_on():
+        x = T.tt_reshape(X, (4,))
+        if np.max(np.array(T.tt_ranks(L)) * np.array(T.tt_ranks(x))) <= 80:
+            res = _fused_affine([(1.0, (0, L, x)), (-1.0, b)], e, draws=(len(b),))
+            if res is not None:
+                return res
+    return T.tt_rank_reduce(T.tt_sub(tt_mat_vec_mul(L, T.tt_reshape(X, (4,)), e, st.eps), b), e), None
+
+
 def tt_compute_primal_feasibility(L, b, X, st):
     """`src/tt_ipm.py:404-407`"""
-    e = 0.01 * st.eta * st.primal_error_normalisation
-    return T.tt_rank_reduce(T.tt_sub(tt_mat_vec_mul(L, T.tt_reshape(X, (4,)), e, st.eps), b), e)
+    return _primal_feasibility(L, b, X, st)[0]
+
+
+def _dual_feasibility(C, Ladj, Z, Y, Tt, st):
+    """(`tt_compute_dual_feasibility`, its squared norm where the fused call produced the returned train, else
+    None).  Fused: Ladj Y - Z - C in one rounding (the st.eps roundings of the product and of Z + C are skipped);
+    the active case's - Tt stays the second rounding it was."""
+    act = st.ineq_status is IneqStatus.ACTIVE
+    e = st.eps if act else 0.01 * st.eta * st.dual_error_normalisation
+    res = None
+    if _affine_on():
+        res = _fused_affine([(1.0, (0, Ladj, Y)), (-1.0, T.tt_reshape(Z, (4,))), (-1.0, C)], e, draws=(len(C),))
+    if res is None:
+        res = T.tt_rank_reduce(T.tt_sub(T.tt_fast_matrix_vec_mul(Ladj, Y, st.eps),
+                                        T.tt_rank_reduce(T.tt_add(T.tt_reshape(Z, (4,)), C), st.eps)), e), None
+    df, norm2 = res
+    if act and Tt is not None:
+        df = T.tt_rank_reduce(T.tt_sub(df, T.tt_reshape(Tt, (4,))), 0.01 * st.eta * st.dual_error_normalisation)
+        norm2 = None
+    return df, norm2
 
 
 def tt_compute_dual_feasibility(C, Ladj, Z, Y, Tt, st):
     """`src/tt_ipm.py:410-417`"""
-    act = st.ineq_status is IneqStatus.ACTIVE
-    df = T.tt_rank_reduce(T.tt_sub(T.tt_fast_matrix_vec_mul(Ladj, Y, st.eps),
-                                   T.tt_rank_reduce(T.tt_add(T.tt_reshape(Z, (4,)), C), st.eps)),
-                          st.eps if act else 0.01 * st.eta * st.dual_error_normalisation)
-    if act and Tt is not None:
-        df = T.tt_rank_reduce(T.tt_sub(df, T.tt_reshape(Tt, (4,))), 0.01 * st.eta * st.dual_error_normalisation)
-    return df
+    return _dual_feasibility(C, Ladj, Z, Y, Tt, st)[0]
+
+
+def _tt_project_symmetrise(Y, P, e, st):
+    """The Y update's `sym(Y - P Y)` on the flat train Y (middle 4 = (2, 2)): fused, one 4-term call on Y, P Y and
+    their transposes with the weights +-0.5 (the st.eps rounding of P Y is skipped)."""
+    if _affine_on():
+        PY = (0, P, Y)
+        res = _fused_affine([(0.5, Y), (-0.5, PY), (0.5, Y, True), (-0.5, PY, True)], e, draws=(len(Y), len(Y)),
+                            mids=(2, 2))
+        if res is not None:
+            return T.tt_reshape(res[0], (4,))
+    return T.tt_reshape(_tt_symmetrise(T.tt_reshape(T.tt_sub(Y, T.tt_fast_matrix_vec_mul(P, Y, st.eps)), (2, 2)), e),
+                        (4,))
+
+
+def _tt_boundary_masked(mask, X, st):
+    """`bv mask + mask o X` rounded at st.eps: fused, one call (the st.eps rounding of mask o X is skipped)"""
+    if _affine_on() and mask[0].dim() == 4 and X[0].dim() == 4:
+        res = _fused_affine([(_f32(st.ineq_boundary_val), mask), (1.0, (3, mask, X))], st.eps, draws=(len(mask),))
+        if res is not None:
+            return res[0]
+    return T.tt_rank_reduce(T.tt_add(T.tt_scale(st.ineq_boundary_val, mask), T.tt_fast_hadamard(mask, X, st.eps)),
+                            eps=st.eps)
 
 
 def tt_compute_centrality(X, Z, st):
@@ -624,8 +694,8 @@ def tt_infeasible_newton_system(lhs, C, X, Y, Z, Tt, L, Ladj, b, mask, st):
     # same steps in the same order: the random core picks of tt_scale stay where they were); the
     # centrality row is built there too when it is certain to be (not central), and its norm -- the
     # KKT row scaling's (`_tt_kkt_row_scales`) -- comes back in the same read
-    pf = tt_compute_primal_feasibility(L, b, X, st)
-    df = tt_compute_dual_feasibility(C, Ladj, Z, Y, Tt, st)
+    pf, pf2 = _primal_feasibility(L, b, X, st)
+    df, df2 = _dual_feasibility(C, Ladj, Z, Y, Tt, st)
     if st.aho_direction:
         lhs[2, 1] = T.tt_psd_rank_reduce(T.tt_scale(0.5, T.tt_add(T.tt_IkronM(Z), T.tt_MkronI(Z))),
                                          eps=0.1 * st.eta * st.dual_error_normalisation)
@@ -635,8 +705,12 @@ def tt_infeasible_newton_system(lhs, C, X, Y, Z, Tt, L, Ladj, b, mask, st):
         lhs[2, 1] = T.tt_psd_rank_reduce(T.tt_MkronI(Z), eps=0.1 * st.eta * st.dual_error_normalisation)
         lhs[2, 2] = T.tt_psd_rank_reduce(T.tt_IkronM(X), eps=0.1 * st.eta * st.primal_error_normalisation)
     cen = None if st.is_central else tt_compute_centrality(X, Z, st)
-    ips = T.tt_scalars([("ip", pf, pf), ("ip", df, df)] + ([("ip", cen, cen)] if cen is not None else []))
-    npf, ndf = T.norm_from_ip(ips[0]), T.norm_from_ip(ips[1])
+    # a residual from the fused rounding brings its squared norm along (the one read that call makes anyway)
+    specs = [("ip", r, r) for r, n2 in ((pf, pf2), (df, df2)) if n2 is None] + (
+        [("ip", cen, cen)] if cen is not None else [])
+    ips = iter(T.tt_scalars(specs) if specs else [])
+    npf = T.norm_from_ip(pf2 if pf2 is not None else next(ips))
+    ndf = T.norm_from_ip(df2 if df2 is not None else next(ips))
     st.primal_error = np.divide(npf, st.primal_error_normalisation)
     st.is_primal_feasible = np.less(st.primal_error, st.feasibility_tol)
     st.dual_error = np.divide(ndf, st.dual_error_normalisation)
@@ -653,13 +727,12 @@ def tt_infeasible_newton_system(lhs, C, X, Y, Z, Tt, L, Ladj, b, mask, st):
         rhs._norms[1] = (df, ndf)
     if cen is not None:
         rhs[2] = cen
-        rhs._norms[2] = (cen, T.norm_from_ip(ips[2]))
+        rhs._norms[2] = (cen, T.norm_from_ip(next(ips)))
     elif st.is_last_iter:
         rhs[2] = tt_compute_centrality(X, Z, st)
     if st.ineq_status is IneqStatus.ACTIVE:
         lhs[3, 1] = T.tt_diag_op(Tt, 0.1 * st.eta * st.dual_error_normalisation)
-        mX = T.tt_rank_reduce(T.tt_add(T.tt_scale(st.ineq_boundary_val, mask), T.tt_fast_hadamard(mask, X, st.eps)),
-                              eps=st.eps)
+        mX = _tt_boundary_masked(mask, X, st)
         lhs[3, 3] = T.tt_rank_reduce(T.tt_add(st.lag_map_t, T.tt_diag_op(mX, st.eps)),
                                      eps=0.1 * st.eta * st.dual_error_normalisation)
         if not st.is_central or st.is_last_iter:
@@ -1101,8 +1174,7 @@ def tt_ipm(lag_maps, obj_tt, lin_op_tt, bias_tt, ineq_mask=None, max_iter=100, m
             else:
                 Z = _tt_step_symmetrise(Z, zs, DZ, e_d, 1)
             Y = _tt_add_round(Y, DY, st.eps, zs)
-            Y = T.tt_reshape(_tt_symmetrise(T.tt_reshape(T.tt_sub(Y, T.tt_fast_matrix_vec_mul(st.lag_map_y, Y, st.eps)),
-                                                         (2, 2)), e_d), (4,))
+            Y = _tt_project_symmetrise(Y, st.lag_map_y, e_d, st)
             if st.ineq_status is IneqStatus.ACTIVE:
                 if fin <= 1:
                     Tt = _tt_step_symmetrise(Tt, zs, DT, e_d)

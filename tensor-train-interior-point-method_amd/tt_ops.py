@@ -19,7 +19,7 @@ import os
 import numpy as np
 from . import dev as D
 from . import rng as _rng
-from ._lib import SumTerm
+from ._lib import AffineTerm, SumTerm
 
 def _const(name, arr):
     """Small constant cores, uploaded once per host thread (on that thread's stream)."""
@@ -1122,6 +1122,143 @@ def _prod_native(kind, a, b, eps):
         return None
     plan = _prod_round_one_plan(kind, a, b)
     return None if plan is None else _prod_round_one(plan, _prod_out_modes(kind, a, b), eps, 0)[0]
+
+
+# ------------------------------------------------------------------ rounding a sum of trains and products
+# round(sum_j c_j op_j(T_j)), T_j a train or the core-wise product of two (kind: `ttk_zipup`'s), op_j the identity
+# or the swap of the two middle indices: the solve's residuals L vec(X) - b and Ladj Y - Z - C, its Y update and
+# bv mask + mask o X.  `ttk_affine_round_one` forms every term inside the one-launch rounding's two loads and
+# also returns ||result||^2.  Off by default, like its three siblings.  Nothing here draws from the random stream.
+AFFINE_ROUND_ONE = os.environ.get("TTIPM_AFFINE_ROUND_ONE", "0") == "1"
+AFFINE_TERMS, AFFINE_PRODS = 4, 2  # terms `ttk_affine_round_one` takes, and how many of them may be products
+
+
+def _affine_norm(terms, mids=None):
+    """The terms as (coef, kind, a, b, transposed) with kind -1 and b None for a plain train, and the middle shape
+    of every core of the result: `mids` (one tuple for all cores, or one per core) where given, else that of the
+    first term whose cores have two middle indices (reversed where it enters transposed), else flat."""
+    out = []
+    for t in terms:
+        coef, op, tr = (t[0], t[1], bool(t[2])) if len(t) == 3 else (t[0], t[1], False)
+        if isinstance(op, tuple):
+            kind, a, b = op
+            assert kind in (0, 1, 2, 3) and len(a) == len(b)
+        else:
+            kind, a, b = -1, op, None
+        out.append((float(coef), int(kind), a, b, tr))
+    d = len(out[0][2])
+    assert len(out) >= 1 and all(len(t[2]) == d for t in out)
+    if mids is None:
+        for _, kind, a, b, tr in out:
+            own = _prod_out_modes(kind, a, b) if kind >= 0 else [tuple(c.shape[1:-1]) for c in a]
+            if all(len(m) == 2 for m in own):
+                mids = [m[::-1] if tr else m for m in own]
+                break
+        else:
+            _, kind, a, b, _ = out[0]
+            mids = [(int(np.prod(m)),) for m in (_prod_out_modes(kind, a, b) if kind >= 0
+                                                 else [tuple(c.shape[1:-1]) for c in a])]
+    elif isinstance(mids, tuple):
+        mids = [mids] * d
+    mids = [tuple(int(v) for v in m) for m in mids]
+    assert all(len(m) == 2 for m in mids) or not any(t[4] for t in out), "a transposed term needs two middle indices"
+    return out, mids
+
+
+def _affine_composed(terms, mids):
+    """The operand as a train of its own: every product exactly (the zip-up at eps 0 returns the unrounded
+    Kronecker-bond cores), every term viewed with its own middle shape, then `_sum_composed`."""
+    trains = []
+    for _, kind, a, b, tr in terms:
+        t = list(a) if kind < 0 else (tt_fast_matrix_vec_mul, tt_fast_mat_mat_mul, tt_fast_hadamard,
+                                      tt_fast_hadamard)[kind](a, b, 0.0)
+        trains.append([c.reshape(c.shape[0], *(m[::-1] if tr else m), c.shape[-1]) for c, m in zip(t, mids)])
+    return _sum_composed(trains, [t[0] for t in terms], [t[4] for t in terms])
+
+
+def _affine_round_one_plan(terms, mids):
+    """The arguments of `ttk_affine_round_one` for these terms -- (d, inner, rows, n, terms) -- the summed and the
+    bound ranks, and what keeps the tables alive, or None when the operand does not fit one workgroup's LDS,
+    passes the term limits or has a single core."""
+    d, n = len(mids), len(terms)
+    if d < 2 or n > AFFINE_TERMS or sum(t[1] >= 0 for t in terms) > AFFINE_PRODS:
+        return None
+    I64, P, vp = ctypes.c_int64, ctypes.c_void_p * d, ctypes.c_void_p
+    inner = (I64 * d)(*[int(np.prod(m)) for m in mids])
+    rows = (I64 * d)(*[m[0] for m in mids]) if any(t[4] for t in terms) else None
+    keep, recs = [], []
+    for coef, kind, a, b, tr in terms:
+        ca = [D.contig(c) for c in a]  # the contiguous inputs stay alive until the call is enqueued
+        pa, ar = P(*[c.data_ptr() for c in ca]), (I64 * (d + 1))(*([a[0].shape[0]] + [c.shape[-1] for c in a]))
+        keep += [ca, pa, ar]
+        if kind < 0:
+            recs.append(AffineTerm(-1, int(tr), coef, ctypes.cast(pa, vp), ctypes.cast(ar, vp), None, None, None))
+            continue
+        cb = [D.contig(c) for c in b]
+        pb, br = P(*[c.data_ptr() for c in cb]), (I64 * (d + 1))(*([b[0].shape[0]] + [c.shape[-1] for c in b]))
+        modes = (I64 * (3 * d))(*_zipup_modes(kind, a, b))
+        keep += [cb, pb, br, modes]
+        recs.append(AffineTerm(kind, int(tr), coef, ctypes.cast(pa, vp), ctypes.cast(ar, vp), ctypes.cast(pb, vp),
+                               ctypes.cast(br, vp), ctypes.cast(modes, vp)))
+    arr = (AffineTerm * n)(*recs)
+    sums, bound = (I64 * (d + 1))(), (I64 * (d + 1))()
+    if D.lib.ttk_affine_round_one_lds(d, inner, n, arr, sums, bound) < 0:
+        return None
+    return (d, inner, rows, n, arr), list(sums), list(bound), keep
+
+
+def affine_round_one_lds(terms, mids=None):
+    """Bytes of LDS `ttk_affine_round_one` needs for these terms (`tt_affine_rank_reduce`'s), -1 if the operand
+    does not fit one workgroup or passes the limits (AFFINE_TERMS terms, AFFINE_PRODS of them products): the
+    products and the sum are then built and rounded."""
+    terms, mids = _affine_norm(terms, mids)
+    plan = _affine_round_one_plan(terms, mids)
+    if plan is None:
+        return -1
+    d, inner, _, n, arr = plan[0]
+    return int(D.lib.ttk_affine_round_one_lds(d, inner, n, arr, None, None))
+
+
+def _affine_native(terms, eps, mode, mids=None):
+    """(tt, tail factor or None, ||tt||^2) from `ttk_affine_round_one` -- one launch into one fresh buffer sized by
+    the bound ranks, one host read (the ranks, the tail and the squared norm) -- or None where that path is not
+    taken: the switch is off, there is no GPU, d < 2, the operand does not fit or passes the term limits.  The
+    caller's tensors are never written."""
+    if not (AFFINE_ROUND_ONE and D.DEV.type == "cuda"):
+        return None
+    terms, mids = _affine_norm(terms, mids)
+    plan = _affine_round_one_plan(terms, mids)
+    if plan is None:
+        return None
+    (d, inner, rows, n, arr), sums, bound, keep = plan
+    assert bound == retraction_ranks(inner, sums, [1 << 62] * (d - 1)), bound
+    outs = _packed_flat(bound, list(inner))
+    info = D.empty(d + 3)
+    D._stream()
+    D.check(D.lib.ttk_affine_round_one(D.ctx(), d, inner, rows, n, arr, float(eps), mode,
+                                       (ctypes.c_void_p * d)(*[o.data_ptr() for o in outs]), info.data_ptr()),
+            "affine_round_one")
+    got = D.read(info)
+    q = [int(v) for v in got[:d + 1]]
+    tt = [o[:q[k] * inner[k] * q[k + 1]].view(q[k], *mids[k], q[k + 1]) for k, o in enumerate(outs)]
+    return tt, (pow(float(got[d + 1]), 1.0 / (2 * d)) if mode else None), float(got[d + 2])
+
+
+def tt_affine_rank_reduce(terms, eps=1e-18, with_norm2=False, mids=None):
+    """`tt_rank_reduce` of sum_j coef_j op_j(T_j).  `terms`: (coef, train) or (coef, (kind, a, b)) -- the product of
+    the trains a and b, kind 0 matrix x vector, 1 matrix x matrix, 2 / 3 Hadamard of vector / matrix trains --
+    each optionally with a third entry, True where the term enters with its two middle indices swapped.  Weights
+    are taken as given (a caller that mirrors `tt_scale` passes float(np.float32(alpha))).  `mids`: the result's
+    middle shape (one tuple, or one per core) where the terms' own cores do not tell it, e.g. a transposed term
+    stored flat.  With TTIPM_AFFINE_ROUND_ONE=1, on the GPU, for at most AFFINE_TERMS terms, AFFINE_PRODS of them
+    products, that fit (`affine_round_one_lds`): one launch and one host read (`ttk_affine_round_one`), no product
+    and no sum ever built.  Otherwise the products are built exactly, summed (`_sum_composed`) and rounded as
+    today.  with_norm2: returns (tt, ||tt||^2) -- the kernel's own figure, or one `tt_inner_prod`."""
+    res = _affine_native(terms, eps, 0, mids)
+    if res is not None:
+        return (res[0], res[2]) if with_norm2 else res[0]
+    tt = tt_rank_reduce(_affine_composed(*_affine_norm(terms, mids)), eps)
+    return (tt, tt_inner_prod(tt, tt)) if with_norm2 else tt
 
 
 def tt_fast_matrix_vec_mul(mat, vec, eps=1e-18):

@@ -31,6 +31,16 @@ product's norm.  Three paths in one run: today's default (`ttk_zipup`: the produ
 never builds the product.
 
     python tools/bench_round.py prod [reps] [rounds]
+
+`affine` times the rounding of a weighted sum of trains and products, by the same method, at d = 10: the solve's
+residual A x - b, an operator of cores (2,4,4,2) applied to a vector train of ranks 4 minus a train b of ranks 3, and
+the 4-term Y update 0.5 (y - P y) + 0.5 (y - P y)^T on a flat train y of ranks 4 (middle 4 = (2,2)) with an operator
+P of ranks 2, each at eps = 1e-2 of the operand's norm with the products formed at 1e-12.  Three paths in one run:
+today's default (`ttk_zipup`, `tt_sub` / `tt_add`, `ttk_round`), the two sibling switches on (`ttk_prod_round_one`,
+then `ttk_sum_round_one`), and the fused `ttk_affine_round_one`, which builds neither a product nor the sum and
+also returns the squared norm.
+
+    python tools/bench_round.py affine [reps] [rounds]
 """
 import hashlib
 import os
@@ -302,8 +312,105 @@ def main_prod(argv):
         bench_prod(kind, 10, ra, rb, reps, rounds)
 
 
+def bench_affine(update, d, reps, rounds):
+    rng = np.random.default_rng(5)
+
+    def cores(r, mid):
+        rk = [1] + [r] * (d - 1) + [1]
+        return [D.from_numpy(rng.standard_normal((rk[k], *mid, rk[k + 1])) * (0.5 ** np.arange(rk[k + 1])))
+                for k in range(d)]
+
+    A, x, b = cores(2, (4, 4)), cores(4, (4,)), cores(3, (4,))
+    small = 1e-12
+
+    def switches(prod, summ, affine):
+        T.ROUND_ONE, T.PROD_ROUND_ONE, T.SUM_ROUND_ONE, T.AFFINE_ROUND_ONE = False, prod, summ, affine
+
+    if update:
+        Ax = (0, A, x)
+        terms, mids = [(0.5, x), (-0.5, Ax), (0.5, x, True), (-0.5, Ax, True)], (2, 2)
+        what_is = "Y update 0.5 (y - P y) + 0.5 (y - P y)^T, P ranks 2, y ranks 4 (summed 24)"
+    else:
+        terms, mids = [(1.0, (0, A, x)), (-1.0, b)], None
+        what_is = "A x - b, operator (r,4,4,R) ranks 2 x vector ranks 4 minus b ranks 3 (summed 11)"
+    lds = T.affine_round_one_lds(terms, mids)
+    assert lds >= 0
+    switches(False, False, False)
+    eps = 1e-2 * T.tt_norm(T._affine_composed(*T._affine_norm(terms, mids)))
+
+    def default():
+        switches(False, False, False)
+        if not update:
+            return T.tt_rank_reduce(T.tt_sub(T.tt_fast_matrix_vec_mul(A, x, small), b), eps)
+        M = T.tt_reshape(T.tt_sub(x, T.tt_fast_matrix_vec_mul(A, x, small)), (2, 2))
+        return T.tt_rank_reduce(T.tt_scale(0.5, T.tt_add(M, T.tt_transpose(M))), eps)
+
+    def siblings():
+        switches(True, True, False)
+        Ax_ = T.tt_fast_matrix_vec_mul(A, x, small)
+        if not update:
+            return T.tt_sum_rank_reduce([Ax_, b], [1.0, -1.0], [False, False], eps)
+        y2, p2 = T.tt_reshape(x, (2, 2)), T.tt_reshape(Ax_, (2, 2))
+        return T.tt_sum_rank_reduce([y2, p2, y2, p2], [0.5, -0.5, 0.5, -0.5], [False, False, True, True], eps)
+
+    def fused():
+        switches(False, False, True)
+        return T.tt_affine_rank_reduce(terms, eps, mids=mids)
+
+    what = (("default (ttk_zipup, ttk_round)", default), ("ttk_prod_round_one, ttk_sum_round_one", siblings),
+            ("ttk_affine_round_one", fused))
+    info = {}
+    ref = None
+    for name, f in what:
+        out = f()
+        torch.cuda.synchronize()
+        l0, s0 = D.lib.ttk_launch_count(), D.lib.ttk_sync_count()
+        f()
+        torch.cuda.synchronize()
+        nl, ns = D.lib.ttk_launch_count() - l0, D.lib.ttk_sync_count() - s0
+        dense = T.tt_to_tensor(out)
+        ref = dense if ref is None else ref
+        info[name] = (T.tt_ranks(out), nl, ns, float(np.linalg.norm(dense - ref) / np.linalg.norm(ref)))
+        for _ in range(20):  # warm-up of every shape the timed window uses
+            f()
+    torch.cuda.synchronize()
+    times = {name: [] for name, _ in what}
+    for _ in range(rounds):
+        for name, f in what:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                f()
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) / reps * 1e6)
+    switches(False, False, False)
+    print(f"d={d} {what_is}, eps {eps:g}; LDS {lds} bytes; {reps} calls x {rounds} rounds, us per call", flush=True)
+    for name, _ in what:
+        t = np.array(times[name])
+        rk, nl, ns, err = info[name]
+        print(f"{name:38s} median {np.median(t):8.1f}  min {t.min():8.1f}  max {t.max():8.1f}  launches {nl:3d}  "
+              f"host waits {ns:2d}  |out - default|/|default| {err:.2e}  ranks {rk}", flush=True)
+    old, sib, new = (np.array(times[name]) for name, _ in what)
+    for other, t in (("the default", old), ("the two sibling calls", sib)):
+        spread = max(t.max() - t.min(), new.max() - new.min())
+        gap = float(np.median(t) - np.median(new))
+        print(f"ttk_affine_round_one: {np.median(t) / np.median(new):.2f}x {other} (medians {gap:.1f} us apart, min-max "
+              f"spread {spread:.1f} us: {'beyond' if abs(gap) > spread else 'within'} the spread)", flush=True)
+    print(flush=True)
+
+
+def main_affine(argv):
+    reps = int(argv[0]) if argv else 100
+    rounds = int(argv[1]) if len(argv) > 1 else 7
+    assert torch.cuda.is_available(), "bench_round needs an MI355X"
+    for update in (False, True):
+        bench_affine(update, 10, reps, rounds)
+
+
 if __name__ == "__main__":
-    if sys.argv[1:2] == ["prod"]:
+    if sys.argv[1:2] == ["affine"]:
+        main_affine(sys.argv[2:])
+    elif sys.argv[1:2] == ["prod"]:
         main_prod(sys.argv[2:])
     elif sys.argv[1:2] == ["one"]:
         main_one(sys.argv[2:])
