@@ -734,6 +734,37 @@ int64_t ttk_affine_round_one_lds(int d, const int64_t *inner, int nterms, const 
 int ttk_affine_round_one(ttk_ctx ctx, int d, const int64_t *inner, const int64_t *rows, int nterms,
                          const ttk_affine_term *terms, double eps, int mode, double *const *out, double *info);
 
+/* The truncate-and-kick split of a two-site local solve in one launch (`_add_kick_rank`,
+ * `_add_kick_rank_rev`, src/tt_als.py:1041-1053, as `_step_size_local_solve` ends with them, :1023-1037;
+ * with S NULL and p = r, `add_kick_rank`, cy_src/tt_ops_cy.pyx:557-578): one workgroup stages the
+ * concatenated matrix column-major in LDS, factors it with Householder reflectors (LAPACK's sign convention,
+ * m < n handled), forms Q and multiplies the triangular factor into diag(S[:r]) Vt[:r], which it reads from
+ * global memory.  The rank r is the caller's decision on the singular values it has read; the output rank
+ * q is host arithmetic; the kernel decides nothing, nothing is read back and the call returns after
+ * enqueueing one launch on the context's stream.
+ * rev = 0: U (a x p), Vt (p x b), G (a x r_add), the Gaussian block.  cat = [U[:, :r] | G] (a x (r + r_add))
+ * = Q R, economic, q = min(a, r + r_add); s1 = Q (a x q), s2 = R[:, :r] (diag(S[:r]) Vt[:r]) (q x b).
+ * rev = 1 (the SVD of the transposed unfolding): U (b x p), Vt (p x a), G (r_add x b).
+ * cat = [U[:, :r]^T ; G] ((r + r_add) x b) = Rm Q, economic, Q with orthonormal rows, q = min(r + r_add, b),
+ * computed as the QR of the transpose with its rows and columns reversed (J the anti-identity):
+ * J cat^T J = Qt Rt, Rm = J Rt^T J, Q = J Qt^T J; s1 = (diag(S[:r]) Vt[:r])^T Rm[:r] (a x q), s2 = Q (q x b).
+ * This is LAPACK's dgerqf reflector for reflector (the pivot of a row is its last entry), so Rm and Q have the
+ * gauge of scipy.linalg.rq.  A QR of cat^T J alone (the columns reversed, not the rows) pivots on a row's first
+ * entry and gives the same factors up to the signs of Q's rows and of Rm's columns; s1 s2 is the same.
+ * S: p doubles, or NULL for all ones.  Every matrix row-major, contiguous, fp64, on the device; inputs are
+ * read only and no output overlaps an input.  An S of zeros gives a finite zero product.  Each product
+ * element is one fma chain with k ascending, diag(S) Vt rounded first; the reductions are fixed wave trees:
+ * two calls on the same input give the same bits.
+ * ttk_split_kick_lds (host only): the bytes of LDS, or -1 when the concatenated matrix and Q do not fit one
+ * workgroup (at most 160 KiB, every extent at most the LDS capacity in doubles) or the arguments are
+ * invalid -- the caller then composes the split from ttk_copy_nd, ttk_qr and ttk_einsum; fills *q_out
+ * unless NULL.  ttk_split_kick validates on the host (rev 0 or 1, every extent >= 1, r <= p, p <= min(a, b)
+ * where S is given, no null pointer but S, the LDS fit) and returns TTK_ERR_ARG without launching when a
+ * check fails. */
+int64_t ttk_split_kick_lds(int rev, int a, int b, int p, int r, int r_add, int64_t *q_out);
+int ttk_split_kick(ttk_ctx ctx, int rev, int a, int b, int p, int r, int r_add, const double *U, const double *S,
+                   const double *Vt, const double *G, double *s1, double *s2);
+
 /* Dense Schur-complement local KKT solve in one call (SURVEY §8(b) `ttk_local_assemble` +
  * `ttk_dense_schur_solve`; the dense branch of `_ipm_local_solver`, src/tt_ipm.py:183-229):
  * assembles L_XI = B22 diag(inv_I), L_eq = B01, L_Z = B21 (each 'lsr,smnS,LSR->lmLrnR'), Cholesky of

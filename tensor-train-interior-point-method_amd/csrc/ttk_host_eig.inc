@@ -33,6 +33,9 @@ using trsm_fn = int (*)(void *, const double *, int, double *, int, int, int);
 using ray_dev_fn = int (*)(void *, const double *, double *, int64_t, double *);
 using ray_sync_fn = int (*)(void *, const double *, double *, int64_t, double *, double *);
 using batch_fn = int (*)(void *);
+using split_kick_lds_fn = int64_t (*)(int, int, int, int, int, int, int64_t *);
+using split_kick_fn = int (*)(void *, int, int, int, int, int, int, const double *, const double *, const double *,
+                              const double *, double *, double *);
 
 struct Fns {
   svd_work_fn svd_work = nullptr;
@@ -49,6 +52,8 @@ struct Fns {
   ray_dev_fn ray_dev = nullptr;
   ray_sync_fn ray_sync = nullptr;
   batch_fn batch_begin = nullptr, batch_end = nullptr;
+  split_kick_lds_fn split_kick_lds = nullptr;  // ttk_split_kick_lds, ttk_split_kick (optional 16th, 17th address)
+  split_kick_fn split_kick = nullptr;
 } F;
 
 // ---------------------------------------------------------------- NumPy's legacy Gaussian stream
@@ -304,6 +309,7 @@ struct Solver {
   MT mt;
   double tol = 1e-8, trunc_tol = 0.0;
   int64_t size_limit = 256, max_rank = 1, max_dense = 4096;
+  bool split_kick = false;  // dev.SPLIT_KICK as this call found it
   // _Deferred: (ev, ||r||^2) per dense local solve of a half-sweep, read once after it
   at::Tensor dbuf;
   int dn = 0;
@@ -446,22 +452,25 @@ struct Solver {
     at::Tensor a, b;
     int64_t r;
   };
-  Kick kick(const at::Tensor &u, const at::Tensor &v, int64_t r_add) {  // src/tt_als.py:1041-1046
-    const int64_t old = u.size(-1), rows = u.size(0);
-    std::vector<double> h((size_t)(rows * r_add));
+  at::Tensor gauss(int64_t rows, int64_t cols) {  // RandomState.randn(rows, cols), uploaded
+    std::vector<double> h((size_t)(rows * cols));
     for (auto &e : h) e = mt.next_gauss();
-    at::Tensor uk = o.upload(h, {rows, r_add});
+    return o.upload(h, {rows, cols});
+  }
+  // src/tt_als.py:1041-1046; uk0: the Gaussian block when already drawn
+  Kick kick(const at::Tensor &u, const at::Tensor &v, int64_t r_add, const at::Tensor &uk0) {
+    const int64_t old = u.size(-1), rows = u.size(0);
+    at::Tensor uk = uk0.defined() ? uk0 : gauss(rows, r_add);
     at::Tensor cat = o.emp({rows, old + r_add});
     copy_(cat.slice(1, 0, old), u, 1.0, 0.0);
     copy_(cat.slice(1, old, old + r_add), uk, 1.0, 0.0);
     auto QR = o.qr(cat);
     return {QR.first, o.matmul(QR.second.slice(1, 0, old), v), QR.first.size(-1)};
   }
-  Kick kick_rev(const at::Tensor &u, const at::Tensor &v, int64_t r_add) {  // src/tt_als.py:1048-1053
+  // src/tt_als.py:1048-1053; uk0 as in kick
+  Kick kick_rev(const at::Tensor &u, const at::Tensor &v, int64_t r_add, const at::Tensor &uk0) {
     const int64_t old = v.size(0), cols = v.size(-1);
-    std::vector<double> h((size_t)(r_add * cols));
-    for (auto &e : h) e = mt.next_gauss();
-    at::Tensor uk = o.upload(h, {r_add, cols});
+    at::Tensor uk = uk0.defined() ? uk0 : gauss(r_add, cols);
     at::Tensor cat = o.emp({old + r_add, cols});
     copy_(cat.slice(0, 0, old), v, 1.0, 0.0);
     copy_(cat.slice(0, old, old + r_add), uk, 1.0, 0.0);
@@ -472,15 +481,33 @@ struct Solver {
   std::pair<at::Tensor, at::Tensor> split(const at::Tensor &sol, const std::array<int64_t, 4> &sh, bool bwd,
                                           const Ops::SVD *pre) {
     Ops::SVD p = pre ? *pre : split_svd(sol, sh, bwd, c10::nullopt);
+    at::Tensor G;
+    if (split_kick && F.split_kick && F.split_kick_lds) {  // tt_eig._split under dev.SPLIT_KICK: one launch
+      const int64_t r = std::min(prune(p.s.data(), (int64_t)p.s.size(), trunc_tol), max_rank);
+      const int a = (int)(sh[0] * sh[1]), b = (int)(sh[2] * sh[3]), pp = (int)p.U.size(1);
+      int64_t q = 0;
+      if (F.split_kick_lds(bwd ? 1 : 0, a, b, pp, (int)r, 4, &q) >= 0) {
+        G = bwd ? gauss(4, b) : gauss(a, 4);
+        if (p.U.is_contiguous() && p.S.is_contiguous() && p.Vt.is_contiguous()) {
+          at::Tensor s1 = o.emp({a, q}), s2 = o.emp({q, b});
+          // a null context: the one dev._stream() bound to this thread
+          o.ok(F.split_kick(nullptr, bwd ? 1 : 0, a, b, pp, (int)r, 4, p.U.data_ptr<double>(), p.S.data_ptr<double>(),
+                            p.Vt.data_ptr<double>(), G.data_ptr<double>(), s1.data_ptr<double>(),
+                            s2.data_ptr<double>()),
+               "split_kick");
+          return {s1.view({sh[0], sh[1], q}), s2.view({q, sh[2], sh[3]})};
+        }
+      }
+    }
     if (bwd) {
       at::Tensor v = o.E("r,rj->rj", {p.S, p.Vt});
       const int64_t r = std::min(prune(p.s.data(), (int64_t)p.s.size(), trunc_tol), max_rank);
-      Kick k = kick_rev(v.slice(0, 0, r).t(), p.U.slice(1, 0, r).t(), 4);
+      Kick k = kick_rev(v.slice(0, 0, r).t(), p.U.slice(1, 0, r).t(), 4, G);
       return {o.contig(k.a).view({sh[0], sh[1], k.r}), o.contig(k.b).view({k.r, sh[2], sh[3]})};
     }
     const int64_t r = std::min(prune(p.s.data(), (int64_t)p.s.size(), trunc_tol), max_rank);
     at::Tensor s2 = o.E("r,rj->rj", {p.S.slice(0, 0, r), p.Vt.slice(0, 0, r)});
-    Kick k = kick(p.U.slice(1, 0, r), s2, 4);
+    Kick k = kick(p.U.slice(1, 0, r), s2, 4, G);
     return {o.contig(k.a).view({sh[0], sh[1], k.r}), o.contig(k.b).view({k.r, sh[2], sh[3]})};
   }
 
@@ -720,7 +747,7 @@ pybind11::tuple eig_als(const std::vector<at::Tensor> &A, const std::vector<at::
                         const std::vector<at::Tensor> &x0, const at::Tensor &o3, int64_t nswp, double tol,
                         int64_t size_limit, double trunc_tol, int64_t max_rank, int64_t max_dense,
                         pybind11::array_t<uint32_t, pybind11::array::c_style | pybind11::array::forcecast> key,
-                        int64_t pos, int64_t has_gauss, double gauss) {
+                        int64_t pos, int64_t has_gauss, double gauss, bool split_kick) {
   TORCH_CHECK(F.svd_tol && F.batch_end, "ttk_host_bind: bind_eig() not called");
   TORCH_CHECK(g_einsum && g_axpby, "ttk_host_bind: bind() / bind2() not called");  // (g_stream may be the null stream)
   TORCH_CHECK(key.size() == 624, "eig_als: MT19937 key of ", key.size(), " words");
@@ -736,6 +763,7 @@ pybind11::tuple eig_als(const std::vector<at::Tensor> &A, const std::vector<at::
   s.size_limit = size_limit;
   s.max_rank = max_rank;
   s.max_dense = max_dense;
+  s.split_kick = split_kick;
   std::vector<at::Tensor> x = x0;
   int status = 0;
   std::string why;
@@ -795,7 +823,7 @@ int64_t prune_singular_vals(pybind11::array_t<double, pybind11::array::c_style |
 }
 
 void bind_eig(const std::vector<int64_t> &a) {
-  TORCH_CHECK(a.size() == 14 || a.size() == 15, "bind_eig: ", a.size(), " addresses");
+  TORCH_CHECK(a.size() == 14 || a.size() == 15 || a.size() == 17, "bind_eig: ", a.size(), " addresses");
   F.svd_work = reinterpret_cast<svd_work_fn>(a[0]);
   F.svd_tol = reinterpret_cast<svd_tol_fn>(a[1]);
   F.qr_work = reinterpret_cast<qr_work_fn>(a[2]);
@@ -810,7 +838,9 @@ void bind_eig(const std::vector<int64_t> &a) {
   F.ray_sync = reinterpret_cast<ray_sync_fn>(a[11]);
   F.batch_begin = reinterpret_cast<batch_fn>(a[12]);
   F.batch_end = reinterpret_cast<batch_fn>(a[13]);
-  F.svd_read = a.size() > 14 ? reinterpret_cast<svd_read_fn>(a[14]) : nullptr;
+  F.svd_read = a.size() > 14 ? reinterpret_cast<svd_read_fn>(a[14]) : nullptr;  // 0 where the library lacks it
+  F.split_kick_lds = a.size() > 16 ? reinterpret_cast<split_kick_lds_fn>(a[15]) : nullptr;
+  F.split_kick = a.size() > 16 ? reinterpret_cast<split_kick_fn>(a[16]) : nullptr;
 }
 
 }  // namespace eig

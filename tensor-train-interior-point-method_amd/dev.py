@@ -710,6 +710,43 @@ def rq(M):
     return R, Q
 
 
+# `ttk_split_kick` for the truncate-and-kick splits (tt_eig._split, tt_ops.add_kick_rank): off by default, like
+# TTIPM_ROUND_ONE.  A module attribute, read at every call, so that a test can switch it.
+SPLIT_KICK = os.environ.get("TTIPM_SPLIT_KICK", "0") == "1"
+
+
+def split_kick_q(rev, a, b, p, r, r_add):
+    """The output rank q of `ttk_split_kick` on these extents, or None where that call cannot be made: the
+    device is the CPU, the library lacks the entry point, or the working set does not fit one workgroup
+    (`ttk_split_kick_lds` returns -1).  Host arithmetic only: a caller asks before it draws the Gaussian block."""
+    if DEV.type != "cuda" or not hasattr(lib, "ttk_split_kick"):
+        return None
+    q = ctypes.c_int64(0)
+    if lib.ttk_split_kick_lds(int(rev), int(a), int(b), int(p), int(r), int(r_add), ctypes.byref(q)) < 0:
+        return None
+    return int(q.value)
+
+
+def split_kick(rev, U, S, Vt, r, G):
+    """`ttk_split_kick`: the QR of the kicked factor and its product with diag(S[:r]) Vt[:r] in one launch, no
+    host read.  rev 0: U (a, p), Vt (p, b), G (a, r_add); rev 1: U (b, p), Vt (p, a), G (r_add, b); S (p,) or
+    None for all ones.  Returns (s1 (a, q), s2 (q, b), q), or None where the call cannot be made
+    (`split_kick_q`, or an operand that is not contiguous) and the caller composes the split as before."""
+    if not (U.is_contiguous() and Vt.is_contiguous() and G.is_contiguous() and (S is None or S.is_contiguous())):
+        return None
+    p = U.shape[1]
+    a, b = (Vt.shape[1], U.shape[0]) if rev else (U.shape[0], Vt.shape[1])
+    r_add = G.shape[0] if rev else G.shape[1]
+    q = split_kick_q(rev, a, b, p, r, r_add)
+    if q is None:
+        return None
+    s1, s2 = empty(a, q), empty(q, b)
+    _stream()
+    check(lib.ttk_split_kick(ctx(), int(rev), a, b, p, int(r), r_add, _p(U), None if S is None else _p(S), _p(Vt),
+                             _p(G), _p(s1), _p(s2)), "split_kick")
+    return s1, s2, q
+
+
 def cholesky_(A):
     """In-place lower Cholesky; raises LinAlgError if not positive definite."""
     assert A.is_contiguous()

@@ -88,10 +88,11 @@ def _normalise(v):
     return D.scaled(v, 1.0 / D.norm(v))
 
 
-def _kick(u, v, r_add):
-    """`_add_kick_rank` (`src/tt_als.py:1041-1046`)."""
+def _kick(u, v, r_add, uk=None):
+    """`_add_kick_rank` (`src/tt_als.py:1041-1046`); `uk`: the Gaussian block when already drawn."""
     old = u.shape[-1]
-    uk = D.from_numpy(_rng.R().randn(u.shape[0], r_add))
+    if uk is None:
+        uk = D.from_numpy(_rng.R().randn(u.shape[0], r_add))
     cat = D.empty(u.shape[0], old + r_add)
     D.copy_(cat[:, :old], u)
     D.copy_(cat[:, old:], uk)
@@ -99,10 +100,11 @@ def _kick(u, v, r_add):
     return q, D.matmul(Rm[:, :old], v), q.shape[-1]
 
 
-def _kick_rev(u, v, r_add):
-    """`_add_kick_rank_rev` (`src/tt_als.py:1048-1053`)."""
+def _kick_rev(u, v, r_add, uk=None):
+    """`_add_kick_rank_rev` (`src/tt_als.py:1048-1053`); `uk`: the Gaussian block when already drawn."""
     old = v.shape[0]
-    uk = D.from_numpy(_rng.R().randn(r_add, v.shape[-1]))
+    if uk is None:
+        uk = D.from_numpy(_rng.R().randn(r_add, v.shape[-1]))
     cat = D.empty(old + r_add, v.shape[-1])
     D.copy_(cat[:old], v)
     D.copy_(cat[old:], uk)
@@ -120,14 +122,23 @@ def _split_svd(sol, sh, bwd, S_out=None):
 def _split(sol, sh, trunc_tol, max_rank, bwd, pre=None):
     """`pre`: the (U, S, Vt, s) of `_split_svd(sol, ...)` when already computed"""
     U, S, Vt, s = _split_svd(sol, sh, bwd) if pre is None else pre
+    G = None
+    if D.SPLIT_KICK:  # one launch (ttk_split_kick) where it fits; the draw is the composed path's, in its place
+        r = min(T.prune_singular_vals(s, trunc_tol), max_rank)
+        a, b = sh[0] * sh[1], sh[2] * sh[3]
+        if D.split_kick_q(int(bwd), a, b, U.shape[1], r, 4) is not None:
+            G = D.from_numpy(_rng.R().randn(4, b) if bwd else _rng.R().randn(a, 4))
+            out = D.split_kick(int(bwd), U, S, Vt, r, G)
+            if out is not None:
+                return out[0].view(sh[0], sh[1], out[2]), out[1].view(out[2], sh[2], sh[3])
     if bwd:
         v = einsum("r,rj->rj", S, Vt)
         r = min(T.prune_singular_vals(s, trunc_tol), max_rank)
-        s1, s2, r = _kick_rev(v[:r].t(), U[:, :r].t(), 4)  # strided operands: no transpose copies
+        s1, s2, r = _kick_rev(v[:r].t(), U[:, :r].t(), 4, G)  # strided operands: no transpose copies
         return D.contig(s1).view(sh[0], sh[1], r), D.contig(s2).view(r, sh[2], sh[3])
     r = min(T.prune_singular_vals(s, trunc_tol), max_rank)
     s2 = einsum("r,rj->rj", S[:r], Vt[:r])
-    s1, s2, r = _kick(U[:, :r], s2, 4)  # the kick copies the truncated factor itself
+    s1, s2, r = _kick(U[:, :r], s2, 4, G)  # the kick copies the truncated factor itself
     return D.contig(s1).view(sh[0], sh[1], r), D.contig(s2).view(r, sh[2], sh[3])
 
 
@@ -498,11 +509,15 @@ def _native_eig():
     if not _NATIVE_BOUND:
         import ctypes
         L = D.lib
-        B.bind_eig([ctypes.cast(f, ctypes.c_void_p).value for f in (
+        addr = [ctypes.cast(f, ctypes.c_void_p).value for f in (
             L.ttk_svd_work, L.ttk_svd_tol, L.ttk_qr_work, L.ttk_qr, L.ttk_syev_extreme_work, L.ttk_syev_extreme,
             L.ttk_read_sync, L.ttk_upload, L.ttk_cholesky_sync, L.ttk_trsm_lower, L.ttk_rayleigh_tail_dev,
             L.ttk_rayleigh_tail_sync, L.ttk_einsum_batch_begin, L.ttk_einsum_batch_end)
-            + ((L.ttk_svd_tol_read,) if D._SVD_READ else ())])
+            + ((L.ttk_svd_tol_read,) if D._SVD_READ else ())]
+        if hasattr(L, "ttk_split_kick"):  # the 16th and 17th address (0 in the 15th: no ttk_svd_tol_read)
+            addr += [0] * (15 - len(addr))
+            addr += [ctypes.cast(f, ctypes.c_void_p).value for f in (L.ttk_split_kick_lds, L.ttk_split_kick)]
+        B.bind_eig(addr)
         _NATIVE_BOUND.append(True)
     D._stream()
     D._fast()  # binds this thread's launch stream in the binder
@@ -532,7 +547,7 @@ def tt_max_generalised_eigen(A, Delta, x0=None, nswp=10, tol=1e-8, size_limit=25
         st = R.get_state()
         status, step, max_res, _, xs, key, pos, hg, g, why = B.eig_als(
             list(A), list(Delta), list(x), o3, int(nswp), float(tol), int(size_limit), float(tol / np.sqrt(d)),
-            int(np.floor(2 ** (d / 2))), MAX_DENSE, st[1], st[2], st[3], st[4])
+            int(np.floor(2 ** (d / 2))), MAX_DENSE, st[1], st[2], st[3], st[4], bool(D.SPLIT_KICK))
         if status == 0:
             NATIVE_CALLS["native"] += 1
             R.set_state(("MT19937", key, pos, hg, g))

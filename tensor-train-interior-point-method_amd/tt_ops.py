@@ -236,6 +236,10 @@ def add_kick_rank(u, v, r_add=2):
     """`cy_src/tt_ops_cy.pyx:557-578`"""
     old_r = u.shape[1]
     uk = D.from_numpy(_rng.R().randn(u.shape[0], r_add))
+    if D.SPLIT_KICK:  # one launch (ttk_split_kick, S absent) where it fits
+        out = D.split_kick(0, u, None, v, old_r, uk)
+        if out is not None:
+            return out
     q, rm = D.qr(_cat(u, uk, -1))
     return q, D.matmul(rm[:, :old_r], v), q.shape[1]
 

@@ -41,6 +41,15 @@ then `ttk_sum_round_one`), and the fused `ttk_affine_round_one`, which builds ne
 also returns the squared norm.
 
     python tools/bench_round.py affine [reps] [rounds]
+
+`kick` times the truncate-and-kick split that ends a two-site local solve of the step-size eigen-ALS
+(`tt_eig._split` on the truncation SVD's factors, the SVD itself outside the clock), by the same method, at
+(a, b, r) = (8, 8, 4), (16, 16, 8) and (64, 64, 28) in both sweep directions, kick rank 4: today's composition
+(scaling, two copies, `ttk_qr`, the product, contiguous copies; the backward split also `dev.rq`'s einsums)
+against the one call `ttk_split_kick` (TTIPM_SPLIT_KICK=1).  Both paths draw the same Gaussian block on the host
+and upload it inside the clock.
+
+    python tools/bench_round.py kick [reps] [rounds]
 """
 import hashlib
 import os
@@ -407,8 +416,76 @@ def main_affine(argv):
         bench_affine(update, 10, reps, rounds)
 
 
+def bench_kick(a, b, r, bwd, reps, rounds):
+    from ttipm_amd import tt_eig as E
+    rng = np.random.default_rng(5)
+    mat = rng.standard_normal((b, a) if bwd else (a, b))
+    Uh, Sh, Vh = np.linalg.svd(mat / np.linalg.norm(mat), full_matrices=False)
+    pre = (D.from_numpy(Uh), D.from_numpy(Sh), D.from_numpy(Vh), Sh)
+    sh = (a, 1, b, 1)
+    lds = D.lib.ttk_split_kick_lds(int(bwd), a, b, len(Sh), r, 4, None)
+    assert lds >= 0
+
+    def call(switch):
+        def f():
+            D.SPLIT_KICK = switch
+            return E._split(None, sh, 1e-30, r, bwd, pre=pre)  # every singular value kept up to max_rank = r
+        return f
+
+    what = (("composed split (the default)", call(False)), ("ttk_split_kick", call(True)))
+    info = {}
+    ref = None
+    for name, f in what:
+        np.random.seed(7)
+        s1, s2 = f()
+        torch.cuda.synchronize()
+        l0, s0 = D.lib.ttk_launch_count(), D.lib.ttk_sync_count()
+        f()
+        torch.cuda.synchronize()
+        nl, ns = D.lib.ttk_launch_count() - l0, D.lib.ttk_sync_count() - s0
+        prod = D.read(s1).reshape(a, -1) @ D.read(s2).reshape(-1, b)
+        ref = prod if ref is None else ref
+        info[name] = (int(s1.shape[-1]), nl, ns, float(np.max(np.abs(prod - ref)) / np.max(np.abs(ref))))
+        for _ in range(20):  # warm-up of every shape the timed window uses
+            f()
+    torch.cuda.synchronize()
+    times = {name: [] for name, _ in what}
+    for _ in range(rounds):
+        for name, f in what:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                f()
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) / reps * 1e6)
+    D.SPLIT_KICK = False
+    print(f"{'backward' if bwd else 'forward'} split a={a} b={b} r={r} kick 4; LDS {lds} bytes; {reps} calls x {rounds} "
+          f"rounds, us per call", flush=True)
+    for name, _ in what:
+        t = np.array(times[name])
+        q, nl, ns, err = info[name]
+        print(f"{name:30s} median {np.median(t):8.1f}  min {t.min():8.1f}  max {t.max():8.1f}  launches {nl:3d}  "
+              f"host waits {ns:2d}  |s1 s2 - default|/|default| {err:.2e}  rank {q}", flush=True)
+    old, new = (np.array(times[name]) for name, _ in what)
+    spread = max(old.max() - old.min(), new.max() - new.min())
+    gap = float(np.median(old) - np.median(new))
+    print(f"ttk_split_kick: {np.median(old) / np.median(new):.2f}x the composed split (medians {gap:.1f} us apart, "
+          f"min-max spread {spread:.1f} us: {'beyond' if abs(gap) > spread else 'within'} the spread)\n", flush=True)
+
+
+def main_kick(argv):
+    reps = int(argv[0]) if argv else 100
+    rounds = int(argv[1]) if len(argv) > 1 else 7
+    assert torch.cuda.is_available(), "bench_round needs an MI355X"
+    for a, b, r in ((8, 8, 4), (16, 16, 8), (64, 64, 28)):
+        for bwd in (False, True):
+            bench_kick(a, b, r, bwd, reps, rounds)
+
+
 if __name__ == "__main__":
-    if sys.argv[1:2] == ["affine"]:
+    if sys.argv[1:2] == ["kick"]:
+        main_kick(sys.argv[2:])
+    elif sys.argv[1:2] == ["affine"]:
         main_affine(sys.argv[2:])
     elif sys.argv[1:2] == ["prod"]:
         main_prod(sys.argv[2:])
