@@ -734,6 +734,41 @@ int64_t ttk_affine_round_one_lds(int d, const int64_t *inner, int nterms, const 
 int ttk_affine_round_one(ttk_ctx ctx, int d, const int64_t *inner, const int64_t *rows, int nterms,
                          const ttk_affine_term *terms, double eps, int mode, double *const *out, double *info);
 
+/* Up to TTK_ROUND_MANY_MAX independent ttk_affine_round_one roundings in one launch: workgroup j of the grid
+ * rounds job j, whose operand, eps, mode and out are exactly ttk_affine_round_one's (d, inner, rows, nterms,
+ * terms, eps, mode, out).  The jobs may differ in d, extents, term count and kinds, eps and mode, and may share
+ * input trains; the inputs are read only, and no output may overlap an input or another job's output.
+ * Layout: the per-job kernel arguments (each job's plan, term tables and pointers) travel as a table of njobs
+ * records in device memory, uploaded stream-ordered on the context's stream through its pinned ring (ttk_upload's)
+ * into the front of the call's one scratch block; the jobs' orthogonalised cores follow it, each job at its own
+ * offset.  info is one device block: job j owns the d_j + 3 doubles at info_off[j] = sum_{i<j} (d_i + 3), with
+ * ttk_affine_round_one's meaning (info[0 .. d] the ranks, info[d+1] the discarded tail, info[d+2] ||result||^2).
+ * The launch declares the largest of the jobs' LDS requests and is as wide as the widest of their plans.
+ * Arithmetic and bits: every workgroup runs ttk_affine_round_one's code with its job's own planned thread count:
+ * the threads a workgroup has beyond that count own no element, column, pair or row and only join the barriers,
+ * and every stride and reduction order follows the planned count, never the launch width.  Job j's output cores
+ * and info words are therefore the bits of ttk_affine_round_one called alone on that job, whatever else the
+ * batch holds, and two calls give the same bits.  No workgroup waits for another (no hand-off, no atomics, no
+ * spin), so the launch does not depend on co-residency.  The call makes one kernel launch and no host wait and
+ * returns after enqueueing.
+ * Limits: 1 <= njobs <= TTK_ROUND_MANY_MAX; per job, ttk_affine_round_one's.
+ * ttk_affine_round_many_lds (host only): the launch's LDS bytes (the largest job's), or -1 when njobs is out of
+ * range, jobs is NULL, or any job is invalid or does not fit (ttk_affine_round_one_lds < 0, eps, mode or rows
+ * invalid); out is not examined.  Fills info_off (njobs + 1 entries, the last one the size of info) and
+ * threads (njobs entries, job j's planned thread count) unless NULL.  ttk_affine_round_many validates on the
+ * host (njobs in range, jobs and info non-null, every check of ttk_affine_round_one on every job) and returns
+ * TTK_ERR_ARG without launching or copying anything when a check fails, all or nothing; the message names the
+ * function and the job. */
+#define TTK_ROUND_MANY_MAX 8
+typedef struct {
+  int d; const int64_t *inner; const int64_t *rows;      /* as ttk_affine_round_one */
+  int nterms; const ttk_affine_term *terms;
+  double eps; int mode;
+  double *const *out;                                    /* d buffers sized by the job's bound ranks */
+} ttk_affine_job;
+int64_t ttk_affine_round_many_lds(int njobs, const ttk_affine_job *jobs, int64_t *info_off, int *threads);
+int ttk_affine_round_many(ttk_ctx ctx, int njobs, const ttk_affine_job *jobs, double *info);
+
 /* The truncate-and-kick split of a two-site local solve in one launch (`_add_kick_rank`,
  * `_add_kick_rank_rev`, src/tt_als.py:1041-1053, as `_step_size_local_solve` ends with them, :1023-1037;
  * with S NULL and p = r, `add_kick_rank`, cy_src/tt_ops_cy.pyx:557-578): one workgroup stages the

@@ -97,6 +97,8 @@ _SIGS = {
     "ttk_prod_round_one": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, f64, i32, vp, vp]),
     "ttk_affine_round_one_lds": (i64, [i32, vp, i32, vp, vp, vp]),
     "ttk_affine_round_one": (i32, [vp, i32, vp, vp, i32, vp, f64, i32, vp, vp]),
+    "ttk_affine_round_many_lds": (i64, [i32, vp, vp, vp]),
+    "ttk_affine_round_many": (i32, [vp, i32, vp, vp]),
     "ttk_split_kick_lds": (i64, [i32, i32, i32, i32, i32, i32, vp]),
     "ttk_split_kick": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "ttk_dense_schur_solve": (i32, [vp, i64, i64, i64, vp, vp, vp, vp, vp]),
@@ -175,6 +177,12 @@ class AffineTerm(ctypes.Structure):
     """`ttk_affine_term` (include/ttk.h): one term of `ttk_affine_round_one`"""
     _fields_ = [("kind", i32), ("transpose", i32), ("coef", f64), ("a", vp), ("a_ranks", vp), ("b", vp),
                 ("b_ranks", vp), ("modes", vp)]
+
+
+class AffineJob(ctypes.Structure):
+    """`ttk_affine_job` (include/ttk.h): one job of `ttk_affine_round_many`"""
+    _fields_ = [("d", i32), ("inner", vp), ("rows", vp), ("nterms", i32), ("terms", vp), ("eps", f64), ("mode", i32),
+                ("out", vp)]
 
 
 class TTKError(RuntimeError):

@@ -129,6 +129,8 @@ bool gemm_groupable(int nb, int M, int N, int K);
 int gemm_group(hipStream_t st, const GemmProblem *p, int n);
 // ttk_einsum.hip: launch the pending nodes of an open einsum batch (stream order for other launches)
 int batch_barrier(void *stream);
+// ttk_runtime.hip: ttk_upload's copy through the context's pinned ring, without the batch barrier
+int upload_ring(hipStream_t st, const double *host, double *dev, int64_t n);
 // ttk_einsum.hip: one application of the current context's Schur operator handle on `stream`
 int schur_apply(void *stream, int64_t handle, const double *v, double *out);
 }  // namespace ttk

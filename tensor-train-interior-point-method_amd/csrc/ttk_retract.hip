@@ -55,12 +55,19 @@
 // alone also leaves ||result||^2 in info[d + 2]: after phase B every output core but the last has orthonormal
 // columns, so that is the sum of squares of the last carried core, reduced by wave 0 in a fixed order.
 //
+// `ttk_affine_round_many` runs up to TTK_ROUND_MANY_MAX of these roundings in one launch, workgroup j on job j
+// (retract_many_kernel).  The body is the same function (retract_body); the jobs' RtAffineArg records lie in a
+// device-memory table at the front of the call's scratch block, uploaded stream-ordered before the launch, and each
+// workgroup works with its own job's planned thread count whatever the launch width, so every job has the bits
+// of its own `ttk_affine_round_one`.  The workgroups share read-only data only and none waits for another.
+//
 // LDS holds one step's working set, not the train: two carried-core regions that the phases use in
 // turn (QR input / Q, then Z / the Jacobi's rows), one core from global memory or scratch, the
 // rotations G, M and a few small vectors.  The products are VALU fma chains, as in the siblings.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdio>
 
 #include "ttk_common.h"
 #include "ttk_internal.h"
@@ -227,8 +234,9 @@ __device__ __forceinline__ const RtPlan &rt_plan_of(const RtProdArg &a) { return
 __device__ __forceinline__ const RtPlan &rt_plan_of(const RtAffineArg &a) { return a.p; }
 
 // Core k of the train, (r_k, n_k, r_{k+1}) row-major, into dst.  No barrier: the caller's next one publishes it.
-__device__ __forceinline__ void rt_load_core(double *dst, const RtPlan &a, int k) {
-  ro_load(dst, a.core[k], a.r[k] * a.n[k] * a.r[k + 1]);
+// (tid, nt): the team, as in ttk_tt_gemm.h, here and in the three loaders below.
+__device__ __forceinline__ void rt_load_core(double *dst, const RtPlan &a, int k, int tid, int nt) {
+  ro_load(dst, a.core[k], a.r[k] * a.n[k] * a.r[k + 1], tid, nt);
 }
 
 // The element code the operand loaders share, so that equal operands give equal bits.
@@ -267,11 +275,11 @@ __device__ __forceinline__ double rt_prod_elem(bool contract, const double *__re
 // Core k of the summed train: element (a, i, b) belongs to the one term whose row range holds a (every term
 // at k = 0, where R_0 = 1) and whose column range holds b (every term at k = d-1), and is 0.0 if there is
 // none.  Each destination element is written once, by the thread that owns it.
-__device__ __forceinline__ void rt_load_core(double *dst, const RtSumArg &s, int k) {
+__device__ __forceinline__ void rt_load_core(double *dst, const RtSumArg &s, int k, int tid, int nt) {
   const int n = s.p.n[k], R1 = s.p.r[k + 1], nR1 = n * R1, total = s.p.r[k] * nR1;
   const int n1 = s.n1[k], n2 = n / n1;
   const bool first = k == 0, last = k == s.p.d - 1;
-  for (int e = threadIdx.x; e < total; e += blockDim.x) {
+  for (int e = tid; e < total; e += nt) {
     const int a = e / nR1, rem = e - a * nR1, i = rem / R1, b = rem - i * R1;
     double v = 0.0;
     int A = 0, B = 0;
@@ -290,13 +298,13 @@ __device__ __forceinline__ void rt_load_core(double *dst, const RtSumArg &s, int
 
 // Core k of the product train: element (a rb + b, mid, A Rb + B) by rt_prod_elem.  Each destination element is
 // written once, by the thread that owns it.  kind and every extent are uniform across the workgroup.
-__device__ __forceinline__ void rt_load_core(double *dst, const RtProdArg &s, int k) {
+__device__ __forceinline__ void rt_load_core(double *dst, const RtProdArg &s, int k, int tid, int nt) {
   const int rb = s.rb[k], Ra = s.ra[k + 1], Rb = s.rb[k + 1];
   const int m0 = s.m0[k], m1 = s.m1[k], m2 = s.m2[k];
   const int n = s.p.n[k], R1 = s.p.r[k + 1], nR1 = n * R1, total = s.p.r[k] * nR1;
   const double *__restrict__ pa = s.a[k], *__restrict__ pb = s.b[k];
   const bool contract = s.kind < 2;
-  for (int e = threadIdx.x; e < total; e += blockDim.x) {
+  for (int e = tid; e < total; e += nt) {
     const int row = e / nR1, rem = e - row * nR1, mid = rem / R1, col = rem - mid * R1;
     const int a = row / rb, b = row - a * rb, A = col / Rb, B = col - A * Rb;
     dst[e] = rt_prod_elem(contract, pa, pb, a, b, mid, A, B, Ra, Rb, m0, m1, m2, n);
@@ -306,12 +314,12 @@ __device__ __forceinline__ void rt_load_core(double *dst, const RtProdArg &s, in
 // Core k of the affine operand: the owning term as in the sum's loader, the term's middle index remapped first
 // where it is transposed, then the plain element loaded or the product element computed at that index, then
 // the weight.  Each destination element is written once, by the thread that owns it; the term tables are
-// kernel arguments indexed by the uniform j and k.
-__device__ __forceinline__ void rt_load_core(double *dst, const RtAffineArg &s, int k) {
+// kernel arguments (in the batched launch, the job's record) indexed by the uniform j and k.
+__device__ __forceinline__ void rt_load_core(double *dst, const RtAffineArg &s, int k, int tid, int nt) {
   const int n = s.p.n[k], R1 = s.p.r[k + 1], nR1 = n * R1, total = s.p.r[k] * nR1;
   const int n1 = s.n1[k], n2 = n / n1;
   const bool first = k == 0, last = k == s.p.d - 1;
-  for (int e = threadIdx.x; e < total; e += blockDim.x) {
+  for (int e = tid; e < total; e += nt) {
     const int row = e / nR1, rem = e - row * nR1, i = rem / R1, col = rem - i * R1;
     double v = 0.0;
     int A0 = 0, B0 = 0;
@@ -347,8 +355,13 @@ template <> struct RtNorm2<RtAffineArg> { static constexpr bool value = true; };
 // the cores of the summed train (`ttk_sum_round_one`), or RtProdArg, the cores of the product train
 // (`ttk_prod_round_one`), or RtAffineArg, the cores of a weighted sum of trains and products
 // (`ttk_affine_round_one`); it only enters the two rt_load_core calls and, for RtAffineArg, adds info[d + 2].
+//
+// The body is one function for the single-call kernel and the batched one (retract_many_kernel).  (tid, nt) is
+// the team of ttk_tt_gemm.h: the single-call kernels pass (threadIdx.x, blockDim.x) with blockDim.x == p.nt; the
+// batched kernel passes p.nt and TT_IDLE for the threads its wider workgroup has beyond it.  Every loop strides
+// by nt and every reduction is ordered by nt, so the bits are those of a launch with blockDim.x == nt.
 template <bool ADAPT, class Arg>
-__global__ __launch_bounds__(1024) void retract_kernel(const Arg arg, double *scr) {
+__device__ __forceinline__ void retract_body(const Arg &arg, double *scr, const int tid, const int nt) {
   const RtPlan &p = rt_plan_of(arg);
   extern __shared__ __attribute__((aligned(16))) double rt_lds[];
   double *P[2] = {rt_lds + p.oP0, rt_lds + p.oP1};
@@ -356,23 +369,23 @@ __global__ __launch_bounds__(1024) void retract_kernel(const Arg arg, double *sc
   const int d = p.d;
   int cur = 0;
   // ---- phase A: right to left; P[cur] holds the carried core k as (r_k, n_k rho_{k+1})
-  rt_load_core(P[0], arg, d - 1);
+  rt_load_core(P[0], arg, d - 1, tid, nt);
   for (int k = d - 1; k >= 1; --k) {
     const int rk = p.r[k], m = p.n[k] * p.rho[k + 1], kk = p.rho[k], rows = p.r[k - 1] * p.n[k - 1];
     double *Y = P[cur], *Qc = P[cur ^ 1];
-    rt_load_core(C, arg, k - 1);
+    rt_load_core(C, arg, k - 1, tid, nt);
     __syncthreads();
     // the carried core's rows are the columns of its transpose (m x r_k, column-major)
-    ro_householder(Y, m, rk, tau);
-    ro_form_q(Y, tau, m, kk, Qc);
+    ro_householder(Y, m, rk, tau, tid, nt);
+    ro_form_q(Y, tau, m, kk, Qc, tid, nt);
     // Q (m x kk, column-major) is Q^T row-major: the orthogonalised core k (rho_k, n_k, rho_{k+1})
     double *ok = scr + p.so[k];
-    for (int e = threadIdx.x; e < m * kk; e += blockDim.x) ok[e] = Qc[e];
+    for (int e = tid; e < m * kk; e += nt) ok[e] = Qc[e];
     __syncthreads();
     // carried core k-1 (rows x kk) = core_{k-1} (rows x r_k) R^T, R (kk x r_k) the upper trapezoid of Y
     ro_gemm(rows, kk, rk, [&](int i, int c) { return C[i * rk + c]; },
             [&](int c, int j) { return j <= c ? Y[c * m + j] : 0.0; },
-            [&](int i, int j, double v) { Qc[i * kk + j] = v; });
+            [&](int i, int j, double v) { Qc[i * kk + j] = v; }, tid, nt);
     __syncthreads();
     cur ^= 1;
   }
@@ -386,22 +399,22 @@ __global__ __launch_bounds__(1024) void retract_kernel(const Arg arg, double *sc
     const int m = qi * p.n[i], R = p.rho[i + 1], rest = p.n[i + 1] * p.rho[i + 2];
     const bool rowsz = m <= R;  // rotate the rows of Z, else those of Z^T
     const int pp = rowsz ? m : R, n = rowsz ? R : m;
-    ro_load(C, scr + p.so[i + 1], R * rest);
-    for (int e = threadIdx.x; e < m * R; e += blockDim.x) {
+    ro_load(C, scr + p.so[i + 1], R * rest, tid, nt);
+    for (int e = tid; e < m * R; e += nt) {
       const int a = e / R, c = e - a * R;
       A[rowsz ? e : c * m + a] = Z[e];
     }
-    const int *perm = tt_jacobi_svd(A, G, sv, pp, n);
+    const int *perm = tt_jacobi_svd(A, G, sv, pp, n, tid, nt);
     int qn = p.q[i + 1];
     if (ADAPT) {  // one thread decides, one barrier publishes: qn is uniform and 1 <= qn <= pp <= p.q[i + 1]
-      if (threadIdx.x == 0) qd[i + 1] = (double)rt_kept_rank(sv, perm, pp, p.thr2, p.track != 0, &tail);
+      if (tid == 0) qd[i + 1] = (double)rt_kept_rank(sv, perm, pp, p.thr2, p.track != 0, &tail);
       __syncthreads();
       qn = (int)qd[i + 1];
     }
     // rows of Z:   G = U^T, A = diag(S) V^T:  out_i = G^T[:, top],        M = A[top]
     // rows of Z^T: G = V^T, A = diag(S) U^T:  out_i = (A / S)^T[:, top],  M = diag(S) G[top]
     double *oi = p.out[i];
-    for (int e = threadIdx.x; e < m * qn; e += blockDim.x) {
+    for (int e = tid; e < m * qn; e += nt) {
       const int a = e / qn, t = e - a * qn, row = perm[t];
       if (rowsz) {
         oi[e] = G[row * pp + a];
@@ -410,21 +423,21 @@ __global__ __launch_bounds__(1024) void retract_kernel(const Arg arg, double *sc
         oi[e] = sg > 0.0 ? A[row * n + a] / sg : 0.0;
       }
     }
-    for (int e = threadIdx.x; e < qn * R; e += blockDim.x) {
+    for (int e = tid; e < qn * R; e += nt) {
       const int t = e / R, c = e - t * R, row = perm[t];
       Mq[e] = rowsz ? A[row * n + c] : sv[row] * G[row * pp + c];
     }
     __syncthreads();
     // Z (qn x rest) <- M (qn x R) x orthogonalised core i+1 (R x rest)
     ro_gemm(qn, rest, R, [&](int a, int c) { return Mq[a * R + c]; }, [&](int c, int j) { return C[c * rest + j]; },
-            [&](int a, int j, double v) { Z[a * rest + j] = v; });
+            [&](int a, int j, double v) { Z[a * rest + j] = v; }, tid, nt);
     __syncthreads();
     qi = qn;
   }
   if (!ADAPT) qi = p.q[d - 1];
   double *ol = p.out[d - 1];
-  for (int e = threadIdx.x; e < qi * p.n[d - 1]; e += blockDim.x) ol[e] = Z[e];
-  if (ADAPT && threadIdx.x == 0) {  // the ranks (thread 0's own LDS words) and the tail
+  for (int e = tid; e < qi * p.n[d - 1]; e += nt) ol[e] = Z[e];
+  if (ADAPT && tid == 0) {  // the ranks (thread 0's own LDS words) and the tail
     p.info[0] = 1.0;
     for (int k = 1; k < d; ++k) p.info[k] = qd[k];
     p.info[d] = 1.0;
@@ -433,14 +446,37 @@ __global__ __launch_bounds__(1024) void retract_kernel(const Arg arg, double *sc
   if (RtNorm2<Arg>::value) {
     // ||result||^2 = the sum of squares of the last carried core (published by the loop's last barrier): wave 0
     // alone, lane l the elements l, l + 64, ... ascending, then the fixed wave tree
-    if (threadIdx.x < 64) {
+    if (tid < 64) {
       const int cnt = qi * p.n[d - 1];
       double part = 0.0;
-      for (int e = threadIdx.x; e < cnt; e += 64) part = fma(Z[e], Z[e], part);
+      for (int e = tid; e < cnt; e += 64) part = fma(Z[e], Z[e], part);
       part = ttk::wave_sum(part);
-      if (threadIdx.x == 0) p.info[d + 2] = part;
+      if (tid == 0) p.info[d + 2] = part;
     }
   }
+}
+
+template <bool ADAPT, class Arg>
+__global__ __launch_bounds__(1024) void retract_kernel(const Arg arg, double *scr) {
+  retract_body<ADAPT>(arg, scr, threadIdx.x, blockDim.x);
+}
+
+// `ttk_affine_round_many`: one record per job, a table in device memory.  a.p.info already points at the job's
+// words of the call's info block; scr is the job's offset (doubles) into the call's scratch block.
+struct alignas(16) RtManyJob {
+  RtAffineArg a;
+  int64_t scr;
+};
+static_assert(sizeof(RtManyJob) % 16 == 0, "the table is an array of aligned records");
+
+// Workgroup j rounds job j with retract_kernel<true, RtAffineArg>'s body and the job's own team: the launch is as
+// wide as the widest plan, and a workgroup's threads beyond its job's p.nt are TT_IDLE.  The workgroups share
+// nothing but the read-only inputs and the table, and none waits for another.  The record is read through the
+// uniform index blockIdx.x.
+__global__ __launch_bounds__(1024) void retract_many_kernel(const RtManyJob *__restrict__ jobs, double *scr) {
+  const RtManyJob &job = jobs[blockIdx.x];
+  const int nt = job.a.p.nt;
+  retract_body<true>(job.a, scr + job.scr, (int)threadIdx.x < nt ? (int)threadIdx.x : TT_IDLE, nt);
 }
 
 // `ttk_sum_round_one`'s checks on the terms and the plan of the summed train: the bytes of dynamic LDS, -1 when
@@ -600,6 +636,83 @@ int64_t ra_plan(int d, const int64_t *inner, int nterms, const ttk_affine_term *
   }
   for (int k = 0; k < d; ++k) a->n1[k] = (unsigned short)inner[k], a->p.core[k] = nullptr;
   return shm;
+}
+
+// Every check of `ttk_affine_round_one` on one operand, for it and for each job of `ttk_affine_round_many`, and
+// the finished kernel argument (plan, terms, rows, threshold, mode, out, info).  who: the name the message starts
+// with, or null for the planners, which set none.  outs: whether out and info are examined.  Returns TTK_OK with
+// *shm and *words set, else TTK_ERR_ARG.
+int ra_prepare(const char *who, int d, const int64_t *inner, const int64_t *rows, int nterms,
+               const ttk_affine_term *terms, double eps, int mode, bool outs, double *const *out, double *info,
+               RtAffineArg *a, int64_t *words, int64_t *shm) {
+  int64_t sum[TT_MAXD + 1];
+  const bool ok = (!outs || (out && info)) && eps >= 0.0 && eps <= 1.79769313486231570e308 && (mode == 0 || mode == 1);
+  *shm = ok ? ra_plan(d, inner, nterms, terms, a, words, sum) : -2;
+  if (*shm < 0) {
+    if (who)
+      ttk::set_error(*shm == -2
+                         ? "%s: bad arguments (d >= 2, 1 to 4 terms, at most 2 of them products, kind -1 to 3, b, "
+                           "b_ranks and modes null exactly for kind -1, every rank and extent >= 1, boundary ranks 1, "
+                           "a product's middle extent equal to inner, no null pointer, coef finite, transpose 0 or 1, "
+                           "eps finite and >= 0, mode 0 or 1)"
+                         : "%s: the operand does not fit one workgroup's LDS (ttk_affine_round_one_lds)",
+                     who);
+    return TTK_ERR_ARG;
+  }
+  bool transposed = false;
+  for (int j = 0; j < nterms; ++j) transposed |= terms[j].transpose != 0;
+  if (transposed && !rows) {
+    if (who) ttk::set_error("%s: a transposed term needs rows", who);
+    return TTK_ERR_ARG;
+  }
+  for (int k = 0; k < d; ++k) {
+    if (rows && (rows[k] < 1 || inner[k] % rows[k] != 0)) {
+      if (who) ttk::set_error("%s: rows[%d] does not divide inner[%d]", who, k, k);
+      return TTK_ERR_ARG;
+    }
+    if (outs && !out[k]) {
+      if (who) ttk::set_error("%s: null out %d", who, k);
+      return TTK_ERR_ARG;
+    }
+    if (rows) a->n1[k] = (unsigned short)rows[k];
+    a->p.out[k] = outs ? out[k] : nullptr;
+  }
+  const double e = (mode ? eps / 2.0 : eps) / std::sqrt((double)(d - 1));
+  a->p.thr2 = e * e;
+  a->p.track = mode;
+  a->p.info = info;
+  return TTK_OK;
+}
+
+// `ttk_affine_round_many`'s plan: every job prepared (ra_prepare) into tab[j], with its scratch offset behind
+// the table and its info words at the prefix sums of d_j + 3.  *shm the largest LDS request, *nt the largest
+// thread count, *words the scratch block (the table first).  who null: the planner, out and info not examined.
+int rm_plan(const char *who, int njobs, const ttk_affine_job *jobs, double *info, RtManyJob *tab, int64_t *shm,
+            int *nt, int64_t *words, int64_t *info_off) {
+  if (njobs < 1 || njobs > TTK_ROUND_MANY_MAX || !jobs || (who && !info)) {
+    if (who) ttk::set_error("%s: bad arguments (1 to %d jobs, jobs and info non-null)", who, TTK_ROUND_MANY_MAX);
+    return TTK_ERR_ARG;
+  }
+  int64_t scr = (int64_t)njobs * (int64_t)(sizeof(RtManyJob) / sizeof(double)), off = 0;
+  *shm = 0, *nt = 0;
+  for (int j = 0; j < njobs; ++j) {
+    const ttk_affine_job &b = jobs[j];
+    char name[64];
+    if (who) snprintf(name, sizeof name, "%s: job %d", who, j);
+    int64_t w = 0, s = 0;
+    if (const int e = ra_prepare(who ? name : nullptr, b.d, b.inner, b.rows, b.nterms, b.terms, b.eps, b.mode,
+                                 who != nullptr, b.out, info ? info + off : nullptr, &tab[j].a, &w, &s))
+      return e;
+    tab[j].scr = scr;
+    scr += tt_even(w > 0 ? w : 2);
+    if (info_off) info_off[j] = off;
+    off += b.d + 3;
+    *shm = s > *shm ? s : *shm;
+    *nt = tab[j].a.p.nt > *nt ? tab[j].a.p.nt : *nt;
+  }
+  if (info_off) info_off[njobs] = off;
+  *words = scr;
+  return TTK_OK;
 }
 
 }  // namespace
@@ -796,43 +909,42 @@ int ttk_affine_round_one(ttk_ctx ctx, int d, const int64_t *inner, const int64_t
                          const ttk_affine_term *terms, double eps, int mode, double *const *out, double *info) {
   ttk::CtxScope scope(ctx);
   RtAffineArg a;
-  int64_t words = 0, sum[TT_MAXD + 1];
-  const bool ok = out && info && eps >= 0.0 && eps <= 1.79769313486231570e308 && (mode == 0 || mode == 1);
-  const int64_t shm = ok ? ra_plan(d, inner, nterms, terms, &a, &words, sum) : -2;
-  if (const int e = tt_plan_status(
-          shm,
-          "ttk_affine_round_one: bad arguments (d >= 2, 1 to 4 terms, at most 2 of them products, kind -1 to 3, b, "
-          "b_ranks and modes null exactly for kind -1, every rank and extent >= 1, boundary ranks 1, a product's "
-          "middle extent equal to inner, no null pointer, coef finite, transpose 0 or 1, eps finite and >= 0, mode 0 "
-          "or 1)",
-          "ttk_affine_round_one: the operand does not fit one workgroup's LDS (ttk_affine_round_one_lds)"))
+  int64_t words = 0, shm = 0;
+  if (const int e = ra_prepare("ttk_affine_round_one", d, inner, rows, nterms, terms, eps, mode, true, out, info, &a,
+                               &words, &shm))
     return e;
-  bool transposed = false;
-  for (int j = 0; j < nterms; ++j) transposed |= terms[j].transpose != 0;
-  if (transposed && !rows) {
-    ttk::set_error("ttk_affine_round_one: a transposed term needs rows");
-    return TTK_ERR_ARG;
-  }
-  for (int k = 0; k < d; ++k) {
-    if (rows && (rows[k] < 1 || inner[k] % rows[k] != 0)) {
-      ttk::set_error("ttk_affine_round_one: rows[%d] does not divide inner[%d]", k, k);
-      return TTK_ERR_ARG;
-    }
-    if (!out[k]) {
-      ttk::set_error("ttk_affine_round_one: null out %d", k);
-      return TTK_ERR_ARG;
-    }
-    if (rows) a.n1[k] = (unsigned short)rows[k];
-    a.p.out[k] = out[k];
-  }
-  const double e = (mode ? eps / 2.0 : eps) / std::sqrt((double)(d - 1));
-  a.p.thr2 = e * e;
-  a.p.track = mode;
-  a.p.info = info;
   TtScratch w(ttk::ctx().stream);  // the orthogonalised cores 1 .. d-1
   TTK_HIP(w.alloc(words));
   tt_lds_attr(retract_kernel<true, RtAffineArg>, shm);
   hipLaunchKernelGGL((retract_kernel<true, RtAffineArg>), dim3(1), dim3(a.p.nt), (size_t)shm, w.st, a, w.get());
+  TTK_LAUNCH_CHECK();
+  return TTK_OK;
+}
+
+int64_t ttk_affine_round_many_lds(int njobs, const ttk_affine_job *jobs, int64_t *info_off, int *threads) {
+  RtManyJob tab[TTK_ROUND_MANY_MAX];
+  int64_t shm = 0, words = 0;
+  int nt = 0;
+  if (rm_plan(nullptr, njobs, jobs, nullptr, tab, &shm, &nt, &words, info_off)) return -1;
+  for (int j = 0; threads && j < njobs; ++j) threads[j] = tab[j].a.p.nt;
+  return shm;
+}
+
+int ttk_affine_round_many(ttk_ctx ctx, int njobs, const ttk_affine_job *jobs, double *info) {
+  ttk::CtxScope scope(ctx);
+  RtManyJob tab[TTK_ROUND_MANY_MAX];
+  int64_t shm = 0, words = 0;
+  int nt = 0;
+  if (const int e = rm_plan("ttk_affine_round_many", njobs, jobs, info, tab, &shm, &nt, &words, nullptr)) return e;
+  // one stream-ordered block: the table, then every job's orthogonalised cores
+  TtScratch w(ttk::ctx().stream);
+  TTK_HIP(w.alloc(words));
+  if (const int e = ttk::upload_ring(w.st, reinterpret_cast<const double *>(tab), w.get(),
+                                     (int64_t)njobs * (int64_t)(sizeof(RtManyJob) / sizeof(double))))
+    return e;
+  tt_lds_attr(retract_many_kernel, shm);
+  hipLaunchKernelGGL(retract_many_kernel, dim3(njobs), dim3(nt), (size_t)shm, w.st,
+                     reinterpret_cast<const RtManyJob *>(w.get()), w.get());
   TTK_LAUNCH_CHECK();
   return TTK_OK;
 }

@@ -93,8 +93,17 @@ long long ttk_sync_count(void) { return ttk::g_syncs.load(); }
 
 int ttk_upload(void *stream, const double *host, double *dev, int64_t n) {
   if (int brc = ttk::batch_barrier(stream)) return brc;  // an open einsum batch may feed this call
+  return ttk::upload_ring(TTK_STREAM(stream), host, dev, n);
+}
+
+}  // extern "C"
+
+// host -> device through the context's ring of pinned slots, stream-ordered on st; the host block may be
+// reused as soon as this returns
+int ttk::upload_ring(hipStream_t st, const double *host, double *dev, int64_t n) {
+  void *stream = st;
   if (n <= 0) return TTK_OK;
-  ttk::Ctx &c = ttk::ctx();  // host -> device through the context's ring of pinned slots
+  ttk::Ctx &c = ttk::ctx();
   ttk::UpSlot &sl = c.up[c.up_next];
   c.up_next = (c.up_next + 1) % ttk::UP_SLOTS;
   if (sl.pending) {
@@ -116,6 +125,8 @@ int ttk_upload(void *stream, const double *host, double *dev, int64_t n) {
   sl.pending = true;
   return TTK_OK;
 }
+
+extern "C" {
 
 static int g_mapped_reads = getenv("TTK_MAPPED_READS") ? atoi(getenv("TTK_MAPPED_READS")) : 1;
 

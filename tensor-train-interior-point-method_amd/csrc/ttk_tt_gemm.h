@@ -13,20 +13,36 @@
 #include "ttk_common.h"
 #include "ttk_internal.h"
 
+// The team: every helper below exists in two forms.  The one with a trailing (tid, nt) works with nt threads, the
+// caller's thread being number tid of them; the one without is the whole workgroup, (threadIdx.x, blockDim.x).
+// nt is a multiple of 64 and uniform.  A workgroup launched wider than its team (the batched rounding,
+// ttk_retract.hip) passes TT_IDLE as the tid of its surplus waves: every loop over elements, columns, pairs
+// or rows is then empty, every `tid == 0` and `wid == ...` test false, and such a thread only follows the
+// uniform control flow to the barriers.  Which thread owns an element and how a reduction is ordered depend on
+// nt alone, never on blockDim.x, so a team gives the same bits in a wider workgroup.
+constexpr int TT_IDLE = 1 << 30;  // above every element count (those stay below 2^31 / 2) and, >> 6, every wave id
+
 // C(i, j) = sum_k a(i, k) b(k, j), k ascending in one fma chain from 0; element e = i N + j goes to
-// thread e mod blockDim.x.
+// thread e mod nt.
 template <class FA, class FB, class FC>
-__device__ __forceinline__ void ro_gemm(int M, int N, int K, FA a, FB b, FC store) {
-  for (int e = threadIdx.x; e < M * N; e += blockDim.x) {
+__device__ __forceinline__ void ro_gemm(int M, int N, int K, FA a, FB b, FC store, int tid, int nt) {
+  for (int e = tid; e < M * N; e += nt) {
     const int i = e / N, j = e - i * N;
     double acc = 0.0;
     for (int k = 0; k < K; ++k) acc = fma(a(i, k), b(k, j), acc);
     store(i, j, acc);
   }
 }
+template <class FA, class FB, class FC>
+__device__ __forceinline__ void ro_gemm(int M, int N, int K, FA a, FB b, FC store) {
+  ro_gemm(M, N, K, a, b, store, threadIdx.x, blockDim.x);
+}
 
+__device__ __forceinline__ void ro_load(double *dst, const double *src, int n, int tid, int nt) {
+  for (int e = tid; e < n; e += nt) dst[e] = src[e];
+}
 __device__ __forceinline__ void ro_load(double *dst, const double *src, int n) {
-  for (int e = threadIdx.x; e < n; e += blockDim.x) dst[e] = src[e];
+  ro_load(dst, src, n, threadIdx.x, blockDim.x);
 }
 
 __host__ __device__ inline int64_t tt_even(int64_t v) { return (v + 1) & ~(int64_t)1; }  // 16-byte aligned regions
@@ -70,8 +86,8 @@ constexpr double NY_EPS = 2.220446049250313e-16;
 // diagonal gives tau = 0 (H = I).  Every wave forms reflector j itself (the same wave-tree sum of the
 // same lane partials, so the same bits in every wave) and applies it to the columns it owns: one
 // workgroup barrier per column.  Ends with a barrier.
-__device__ void ro_householder(double *Y, int m, int n, double *tau) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+__device__ void ro_householder(double *Y, int m, int n, double *tau, int tid, int nt) {
+  const int lane = tid & 63, wid = tid >> 6, nw = nt >> 6;
   const int k = m < n ? m : n;
   for (int j = 0; j < k; ++j) {
     double *wj = Y + j * m;
@@ -111,13 +127,16 @@ __device__ void ro_householder(double *Y, int m, int n, double *tau) {
   }
   __syncthreads();
 }
+__device__ __forceinline__ void ro_householder(double *Y, int m, int n, double *tau) {
+  ro_householder(Y, m, n, tau, threadIdx.x, blockDim.x);
+}
 
 // Qc (m x k, column-major, in LDS) = H_0 ... H_{k-1} [I_k; 0] from the reflectors ro_householder left
 // in Y.  Column c only meets the reflectors j = c, c-1, ..., 0, so a wave takes whole columns through
 // all their reflectors with no workgroup barrier in between.  Ends with a barrier.
-__device__ void ro_form_q(const double *Y, const double *tau, int m, int k, double *Qc) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  for (int e = threadIdx.x; e < m * k; e += blockDim.x) {
+__device__ void ro_form_q(const double *Y, const double *tau, int m, int k, double *Qc, int tid, int nt) {
+  const int lane = tid & 63, wid = tid >> 6, nw = nt >> 6;
+  for (int e = tid; e < m * k; e += nt) {
     const int c = e / m, i = e - c * m;
     Qc[e] = (i == c) ? 1.0 : 0.0;
   }
@@ -138,13 +157,17 @@ __device__ void ro_form_q(const double *Y, const double *tau, int m, int k, doub
   }
   __syncthreads();
 }
+__device__ __forceinline__ void ro_form_q(const double *Y, const double *tau, int m, int k, double *Qc) {
+  ro_form_q(Y, tau, m, k, Qc, threadIdx.x, blockDim.x);
+}
 
 // One sweep-round of the one-sided Jacobi on the rows of A (p x n) with the rotations accumulated in
 // G (p x p): the round's disjoint pairs (circle method over m = p rounded up to even players, the
 // last one fixed) go to the waves in turn.  A pair (i, j) is rotated when |<a_i, a_j>| exceeds
 // tol ||a_i|| ||a_j||.  Returns after a workgroup barrier.
-__device__ void ny_jacobi_round(double *A, double *G, int p, int n, int m, int round, double tol2, int *flag) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+__device__ void ny_jacobi_round(double *A, double *G, int p, int n, int m, int round, double tol2, int *flag, int tid,
+                                int nt) {
+  const int lane = tid & 63, wid = tid >> 6, nw = nt >> 6;
   for (int t = wid; t < m / 2; t += nw) {
     int i = t == 0 ? m - 1 : (round + t) % (m - 1);
     int j = (round - t + (m - 1)) % (m - 1);
@@ -189,18 +212,18 @@ __device__ void ny_jacobi_round(double *A, double *G, int p, int n, int m, int r
 // Contract: call it once A is written, with no barrier in between.  It sets G, perm and the flags
 // (none of them A), waits at ONE barrier, which also publishes A, then runs at most NY_SWEEPS sweeps,
 // the row norms and the sort.  Ends with a barrier.
-__device__ int *tt_jacobi_svd(double *A, double *G, double *sv, int p, int n) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+__device__ int *tt_jacobi_svd(double *A, double *G, double *sv, int p, int n, int tid, int nt) {
+  const int lane = tid & 63, wid = tid >> 6, nw = nt >> 6;
   int *perm = reinterpret_cast<int *>(sv + tt_even(p));
   int *flag = reinterpret_cast<int *>(sv + 2 * tt_even(p));
-  for (int e = threadIdx.x; e < p * p; e += blockDim.x) G[e] = (e / p == e % p) ? 1.0 : 0.0;
-  for (int e = threadIdx.x; e < NY_SWEEPS; e += blockDim.x) flag[e] = 0;
-  for (int e = threadIdx.x; e < p; e += blockDim.x) perm[e] = e;  // stays a valid index whatever the sort meets
+  for (int e = tid; e < p * p; e += nt) G[e] = (e / p == e % p) ? 1.0 : 0.0;
+  for (int e = tid; e < NY_SWEEPS; e += nt) flag[e] = 0;
+  for (int e = tid; e < p; e += nt) perm[e] = e;  // stays a valid index whatever the sort meets
   __syncthreads();
   const double tol = NY_EPS * (n > 16 ? (double)n : 16.0), tol2 = tol * tol;
   const int m = (p + 1) & ~1;
   for (int sweep = 0; sweep < NY_SWEEPS && p > 1; ++sweep) {
-    for (int round = 0; round < m - 1; ++round) ny_jacobi_round(A, G, p, n, m, round, tol2, flag + sweep);
+    for (int round = 0; round < m - 1; ++round) ny_jacobi_round(A, G, p, n, m, round, tol2, flag + sweep, tid, nt);
     if (flag[sweep] == 0) break;  // written before the round's barrier: every thread reads the same value
   }
   for (int j = wid; j < p; j += nw) {
@@ -210,13 +233,16 @@ __device__ int *tt_jacobi_svd(double *A, double *G, double *sv, int p, int n) {
     if (lane == 0) sv[j] = nrm;
   }
   __syncthreads();
-  for (int j = threadIdx.x; j < p; j += blockDim.x) {
+  for (int j = tid; j < p; j += nt) {
     int pos = 0;
     for (int i = 0; i < p; ++i) pos += (sv[i] > sv[j] || (sv[i] == sv[j] && i < j)) ? 1 : 0;
     perm[pos < p ? pos : p - 1] = j;  // a NaN compares false everywhere: stay in bounds
   }
   __syncthreads();
   return perm;
+}
+__device__ __forceinline__ int *tt_jacobi_svd(double *A, double *G, double *sv, int p, int n) {
+  return tt_jacobi_svd(A, G, sv, p, n, threadIdx.x, blockDim.x);
 }
 
 // ---- host: planning

@@ -614,14 +614,63 @@ def _fused_affine(terms, e, mode=0, draws=(), mids=None):
     return (tt if mode == 0 else T._psd_correct(tt, factor)), norm2
 
 
+def _many_on(*siblings):
+    """whether a group whose members make these single calls ("affine", "sum", "round": `_fused_many`'s) can be
+    batched at all; asked before a call site builds the group's operands"""
+    return (T.AFFINE_ROUND_MANY and _affine_on() and (T.SUM_ROUND_ONE or "sum" not in siblings)
+            and (T.ROUND_ONE or "round" not in siblings))
+
+
+def _fused_many(jobs):
+    """The batched counterpart of `_fused_affine` and `_fused_sum`: several roundings that do not depend on each
+    other in one `ttk_affine_round_many` launch and one host read (TTIPM_AFFINE_ROUND_MANY=1 on top of
+    TTIPM_AFFINE_ROUND_ONE=1, on the GPU), else None: the caller then runs the group as it stands.  jobs: a list of
+    (terms, e, mode, draws, mids, sibling) -- terms, mids and mode as `_fused_affine`'s, draws the lengths of the
+    trains the job's replaced `tt_scale` calls would scale, sibling the single call the job makes when the group
+    runs as it stands: "affine" (`_fused_affine`), "sum" (`_fused_sum`) or "round" (`tt_rank_reduce` /
+    `tt_psd_rank_reduce` of the one plain term).  The batch is taken only where every job would take that single
+    call -- its switch is on and its operand has a plan -- so each job's bits are the sequential code's.  A
+    "round" or "sum" job of one term whose every rank is 1 is returned as it is, unrounded, as those functions
+    return it, and stays out of the launch; at least two jobs must remain.  The `randint`s are drawn job by job in
+    the sequential order (the roundings themselves draw nothing), a tracked job gets `_psd_correct`, and each job
+    comes back as (train, ||train||^2 before the correction, or None for a train returned as it is)."""
+    if not _many_on(*(job[5] for job in jobs)):
+        return None
+    asis = [sibling != "affine" and len(terms) == 1 and all(r == 1 for r in T.tt_ranks(terms[0][1]))
+            for terms, _, _, _, _, sibling in jobs]
+    todo = [job for job, skip in zip(jobs, asis) if not skip]
+    if not 2 <= len(todo) <= T.AFFINE_JOBS:
+        return None
+    res = T._affine_many_native([(terms, e, mode, mids) for terms, e, mode, _, mids, _ in todo])
+    if res is None:
+        return None
+    res = iter(res)
+    out = []
+    for (terms, _, mode, draws, _, _), skip in zip(jobs, asis):
+        tt, factor, norm2 = (terms[0][1], None, None) if skip else next(res)
+        for n in draws:
+            _rng.R().randint(0, n)
+        out.append((tt if mode == 0 else T._psd_correct(tt, factor), norm2))
+    return out
+
+
+def _primal_job(L, b, X, st):
+    """`_fused_affine`'s arguments (terms, e, draws) for L vec(X) - b, or None where `tt_mat_vec_mul` would not take
+    its fast branch"""
+    x = T.tt_reshape(X, (4,))
+    if np.max(np.array(T.tt_ranks(L)) * np.array(T.tt_ranks(x))) > 80:
+        return None
+    return [(1.0, (0, L, x)), (-1.0, b)], 0.01 * st.eta * st.primal_error_normalisation, (len(b),)
+
+
 def _primal_feasibility(L, b, X, st):
     """(`tt_compute_primal_feasibility`, its squared norm where the fused call produced it, else None).  Fused
     only where `tt_mat_vec_mul` would take its fast branch: L vec(X) - b is then rounded once at e, not twice."""
     e = 0.01 * st.eta * st.primal_error_normalisation
     if _affine_on():
-        x = T.tt_reshape(X, (4,))
-        if np.max(np.array(T.tt_ranks(L)) * np.array(T.tt_ranks(x))) <= 80:
-            res = _fused_affine([(1.0, (0, L, x)), (-1.0, b)], e, draws=(len(b),))
+        job = _primal_job(L, b, X, st)
+        if job is not None:
+            res = _fused_affine(job[0], job[1], draws=job[2])
             if res is not None:
                 return res
     return T.tt_rank_reduce(T.tt_sub(tt_mat_vec_mul(L, T.tt_reshape(X, (4,)), e, st.eps), b), e), None
@@ -636,19 +685,75 @@ def _dual_feasibility(C, Ladj, Z, Y, Tt, st):
     """(`tt_compute_dual_feasibility`, its squared norm where the fused call produced the returned train, else
     None).  Fused: Ladj Y - Z - C in one rounding (the st.eps roundings of the product and of Z + C are skipped);
     the active case's - Tt stays the second rounding it was."""
-    act = st.ineq_status is IneqStatus.ACTIVE
-    e = st.eps if act else 0.01 * st.eta * st.dual_error_normalisation
     res = None
     if _affine_on():
-        res = _fused_affine([(1.0, (0, Ladj, Y)), (-1.0, T.tt_reshape(Z, (4,))), (-1.0, C)], e, draws=(len(C),))
+        terms, e, draws = _dual_job(C, Ladj, Z, Y, st)
+        res = _fused_affine(terms, e, draws=draws)
     if res is None:
+        e = _dual_job(C, Ladj, Z, Y, st)[1]
         res = T.tt_rank_reduce(T.tt_sub(T.tt_fast_matrix_vec_mul(Ladj, Y, st.eps),
                                         T.tt_rank_reduce(T.tt_add(T.tt_reshape(Z, (4,)), C), st.eps)), e), None
-    df, norm2 = res
-    if act and Tt is not None:
+    return _dual_active(*res, Tt, st)
+
+
+def _dual_job(C, Ladj, Z, Y, st):
+    """`_fused_affine`'s arguments (terms, e, draws) for Ladj Y - Z - C"""
+    e = st.eps if st.ineq_status is IneqStatus.ACTIVE else 0.01 * st.eta * st.dual_error_normalisation
+    return [(1.0, (0, Ladj, Y)), (-1.0, T.tt_reshape(Z, (4,))), (-1.0, C)], e, (len(C),)
+
+
+def _dual_active(df, norm2, Tt, st):
+    """the active case's second rounding of the dual residual, - Tt; it depends on the first"""
+    if st.ineq_status is IneqStatus.ACTIVE and Tt is not None:
         df = T.tt_rank_reduce(T.tt_sub(df, T.tt_reshape(Tt, (4,))), 0.01 * st.eta * st.dual_error_normalisation)
         norm2 = None
     return df, norm2
+
+
+def _residuals_many(C, L, Ladj, b, X, Y, Z, Tt, st):
+    """((primal residual, ||.||^2), (dual residual, ||.||^2 or None)) with the two fused roundings in one launch
+    (`_fused_many`), else None: the two are then built one after the other"""
+    if not _many_on("affine"):
+        return None
+    pj = _primal_job(L, b, X, st)
+    if pj is None:
+        return None
+    dj = _dual_job(C, Ladj, Z, Y, st)
+    res = _fused_many([(pj[0], pj[1], 0, pj[2], None, "affine"), (dj[0], dj[1], 0, dj[2], None, "affine")])
+    return None if res is None else (res[0], _dual_active(*res[1], Tt, st))
+
+
+def _kron_blocks_many(X, Z, st):
+    """(lhs[2, 1], lhs[2, 2]) of the non-AHO direction, the two tracked roundings in one launch (`_fused_many`),
+    else None"""
+    if not _many_on("round"):
+        return None
+    res = _fused_many([([(1.0, T.tt_MkronI(Z))], 0.1 * st.eta * st.dual_error_normalisation, 1, (), None, "round"),
+                       ([(1.0, T.tt_IkronM(X))], 0.1 * st.eta * st.primal_error_normalisation, 1, (), None, "round")])
+    return None if res is None else (res[0][0], res[1][0])
+
+
+def _step_blocks_many(Dl, act, st):
+    """(DX, DZ, DY, DT before its Hadamard or None) from the solution Dl of a Newton system: the two symmetrised
+    blocks and the one or two plain roundings in one launch (`_fused_many`), else None"""
+    if not _many_on("sum", "round"):
+        return None
+    jobs = []
+    for i in (1, 2):
+        M = T.tt_reshape(_tt_get_block(i, Dl), (2, 2))
+        jobs.append(([(0.5, M), (0.5, M, True)], st.eps, 0, (len(M),), None, "sum"))
+    for i in (0, 3) if act else (0,):
+        jobs.append(([(1.0, _tt_get_block(i, Dl))], st.eps, 0, (), None, "round"))
+    res = _fused_many(jobs)
+    return None if res is None else tuple(r[0] for r in res) + (() if act else (None,))
+
+
+def _add_round_many(pairs, e):
+    """[round(A + B) for A, B in pairs] in one launch (`_fused_many`), else None"""
+    if not _many_on("sum"):
+        return None
+    res = _fused_many([([(1.0, A), (1.0, B)], e, 0, (), None, "sum") for A, B in pairs])
+    return None if res is None else [r[0] for r in res]
 
 
 def tt_compute_dual_feasibility(C, Ladj, Z, Y, Tt, st):
@@ -694,16 +799,24 @@ def tt_infeasible_newton_system(lhs, C, X, Y, Z, Tt, L, Ladj, b, mask, st):
     # same steps in the same order: the random core picks of tt_scale stay where they were); the
     # centrality row is built there too when it is certain to be (not central), and its norm -- the
     # KKT row scaling's (`_tt_kkt_row_scales`) -- comes back in the same read
-    pf, pf2 = _primal_feasibility(L, b, X, st)
-    df, df2 = _dual_feasibility(C, Ladj, Z, Y, Tt, st)
+    res = _residuals_many(C, L, Ladj, b, X, Y, Z, Tt, st)
+    if res is None:
+        pf, pf2 = _primal_feasibility(L, b, X, st)
+        df, df2 = _dual_feasibility(C, Ladj, Z, Y, Tt, st)
+    else:
+        (pf, pf2), (df, df2) = res
     if st.aho_direction:
         lhs[2, 1] = T.tt_psd_rank_reduce(T.tt_scale(0.5, T.tt_add(T.tt_IkronM(Z), T.tt_MkronI(Z))),
                                          eps=0.1 * st.eta * st.dual_error_normalisation)
         lhs[2, 2] = T.tt_psd_rank_reduce(T.tt_scale(0.5, T.tt_add(T.tt_MkronI(X), T.tt_IkronM(X))),
                                          eps=0.1 * st.eta * st.primal_error_normalisation)
     else:
-        lhs[2, 1] = T.tt_psd_rank_reduce(T.tt_MkronI(Z), eps=0.1 * st.eta * st.dual_error_normalisation)
-        lhs[2, 2] = T.tt_psd_rank_reduce(T.tt_IkronM(X), eps=0.1 * st.eta * st.primal_error_normalisation)
+        res = _kron_blocks_many(X, Z, st)
+        if res is None:
+            lhs[2, 1] = T.tt_psd_rank_reduce(T.tt_MkronI(Z), eps=0.1 * st.eta * st.dual_error_normalisation)
+            lhs[2, 2] = T.tt_psd_rank_reduce(T.tt_IkronM(X), eps=0.1 * st.eta * st.primal_error_normalisation)
+        else:
+            lhs[2, 1], lhs[2, 2] = res
     cen = None if st.is_central else tt_compute_centrality(X, Z, st)
     # a residual from the fused rounding brings its squared norm along (the one read that call makes anyway)
     specs = [("ip", r, r) for r, n2 in ((pf, pf2), (df, df2)) if n2 is None] + (
@@ -959,12 +1072,17 @@ def _tt_ipm_newton_step(lhs, rhs, mask, X, Z, Tt, ZX, TX, st, solver):
         Lp, Rp = _tt_build_row_scaled_kkt(lhs, rhs, st, sc)
         Dl, _ = solver(Lp, Rp, st.mals_delta0, st.kkt_iterations + st.is_last_iter, st.mals_rank_restriction, st.eta)
         st.mals_delta0 = Dl
-        DX = _tt_symmetrise(T.tt_reshape(_tt_get_block(1, Dl), (2, 2)), st.eps)
-        DZ = _tt_symmetrise(T.tt_reshape(_tt_get_block(2, Dl), (2, 2)), st.eps)
-        DY = T.tt_rank_reduce(_tt_get_block(0, Dl), eps=st.eps)
-        DT = None
-        if st.ineq_status is IneqStatus.ACTIVE:
-            DT = T.tt_rank_reduce(_tt_get_block(3, Dl), eps=st.eps)
+        res = _step_blocks_many(Dl, st.ineq_status is IneqStatus.ACTIVE, st)
+        if res is None:
+            DX = _tt_symmetrise(T.tt_reshape(_tt_get_block(1, Dl), (2, 2)), st.eps)
+            DZ = _tt_symmetrise(T.tt_reshape(_tt_get_block(2, Dl), (2, 2)), st.eps)
+            DY = T.tt_rank_reduce(_tt_get_block(0, Dl), eps=st.eps)
+            DT = None
+            if st.ineq_status is IneqStatus.ACTIVE:
+                DT = T.tt_rank_reduce(_tt_get_block(3, Dl), eps=st.eps)
+        else:
+            DX, DZ, DY, DT = res
+        if DT is not None:
             DT = T.tt_fast_hadamard(mask, T.tt_reshape(DT, (2, 2)), st.eps)
         xs, zs = _tt_get_step_sizes(X, Z, Tt, DX, DZ, DT, mask, st)
         if not st.is_central and not st.is_last_iter:
@@ -1005,16 +1123,33 @@ def _tt_ipm_newton_step(lhs, rhs, mask, X, Z, Tt, ZX, TX, st, solver):
             Lc, Rc = _tt_build_row_scaled_kkt(lhs, rhs, st, sc)
             Dc, _ = solver(Lc, Rc, st.mals_delta0, st.kkt_iterations + st.is_last_iter, st.mals_rank_restriction, st.eta)
             st.mals_delta0 = Dc
-            DXc = _tt_symmetrise(T.tt_reshape(_tt_get_block(1, Dc), (2, 2)), st.eps)
-            DZc = _tt_symmetrise(T.tt_reshape(_tt_get_block(2, Dc), (2, 2)), st.eps)
-            DYc = T.tt_rank_reduce(_tt_get_block(0, Dc), eps=st.eps)
-            DX = _tt_add_round(DXc, DX, st.eps)
-            DY = _tt_add_round(DYc, DY, st.eps)
-            DZ = _tt_add_round(DZc, DZ, st.eps)
-            if st.ineq_status is IneqStatus.ACTIVE:
-                DTc = T.tt_rank_reduce(_tt_get_block(3, Dc), eps=st.eps)
-                DTc = T.tt_fast_hadamard(mask, T.tt_reshape(DTc, (2, 2)), st.eps)
-                DT = _tt_add_round(DTc, DT, st.eps)
+            # the corrector's blocks, then their sums with the predictor's: no member of either group depends on
+            # another, and only the two symmetrisations draw (in this order); DTc's Hadamard sits between the groups
+            act = st.ineq_status is IneqStatus.ACTIVE
+            res = _step_blocks_many(Dc, act, st)
+            if res is None:
+                DXc = _tt_symmetrise(T.tt_reshape(_tt_get_block(1, Dc), (2, 2)), st.eps)
+                DZc = _tt_symmetrise(T.tt_reshape(_tt_get_block(2, Dc), (2, 2)), st.eps)
+                DYc = T.tt_rank_reduce(_tt_get_block(0, Dc), eps=st.eps)
+                DTc = None
+            else:
+                DXc, DZc, DYc, DTc = res
+                if act:
+                    DTc = T.tt_fast_hadamard(mask, T.tt_reshape(DTc, (2, 2)), st.eps)
+            res = _add_round_many([(DXc, DX), (DYc, DY), (DZc, DZ)] + ([(DTc, DT)] if DTc is not None else []), st.eps)
+            if res is None:
+                DX = _tt_add_round(DXc, DX, st.eps)
+                DY = _tt_add_round(DYc, DY, st.eps)
+                DZ = _tt_add_round(DZc, DZ, st.eps)
+            else:
+                DX, DY, DZ = res[:3]
+            if act:
+                if DTc is None:
+                    DTc = T.tt_rank_reduce(_tt_get_block(3, Dc), eps=st.eps)
+                    DTc = T.tt_fast_hadamard(mask, T.tt_reshape(DTc, (2, 2)), st.eps)
+                    DT = _tt_add_round(DTc, DT, st.eps)
+                else:
+                    DT = res[3] if res is not None else _tt_add_round(DTc, DT, st.eps)
             xs, zs = _tt_get_step_sizes(X, Z, Tt, DX, DZ, DT, mask, st)
         else:
             st.sigma = 0

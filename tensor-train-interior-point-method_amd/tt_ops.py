@@ -19,7 +19,7 @@ import os
 import numpy as np
 from . import dev as D
 from . import rng as _rng
-from ._lib import AffineTerm, SumTerm
+from ._lib import AffineJob, AffineTerm, SumTerm
 
 def _const(name, arr):
     """Small constant cores, uploaded once per host thread (on that thread's stream)."""
@@ -1263,6 +1263,114 @@ def tt_affine_rank_reduce(terms, eps=1e-18, with_norm2=False, mids=None):
         return (res[0], res[2]) if with_norm2 else res[0]
     tt = tt_rank_reduce(_affine_composed(*_affine_norm(terms, mids)), eps)
     return (tt, tt_inner_prod(tt, tt)) if with_norm2 else tt
+
+
+# Several independent affine roundings in one launch, one workgroup each (`ttk_affine_round_many`): the solve
+# issues its residuals, the two Kronecker blocks and the blocks of a Newton step in groups whose members do not
+# depend on each other, and each single call keeps one CU busy while the host waits once per member.  Every job's
+# bits are those of its own `ttk_affine_round_one`.  Off by default, like its siblings; nothing here draws from
+# the random stream.
+AFFINE_ROUND_MANY = os.environ.get("TTIPM_AFFINE_ROUND_MANY", "0") == "1"
+AFFINE_JOBS = 8  # jobs `ttk_affine_round_many` takes (TTK_ROUND_MANY_MAX)
+
+
+def _affine_many_plan(jobs):
+    """The normalised jobs [(terms, eps, mode, mids)], their `_affine_round_one_plan`s and the `ttk_affine_job`
+    table with every `out` still null, or None when there are no jobs, more than AFFINE_JOBS, or one without a
+    plan."""
+    if not 1 <= len(jobs) <= AFFINE_JOBS:
+        return None
+    norm, plans, recs = [], [], []
+    for terms, eps, mode, mids in jobs:
+        terms, mids = _affine_norm(terms, mids)
+        plan = _affine_round_one_plan(terms, mids)
+        if plan is None:
+            return None
+        d, inner, rows, n, arr = plan[0]
+        vp = ctypes.c_void_p
+        norm.append((terms, float(eps), int(mode), mids))
+        plans.append(plan)
+        recs.append(AffineJob(d, ctypes.cast(inner, vp), None if rows is None else ctypes.cast(rows, vp), n,
+                              ctypes.cast(arr, vp), float(eps), int(mode), None))
+    return norm, plans, (AffineJob * len(recs))(*recs)
+
+
+def affine_round_many_lds(jobs):
+    """Bytes of LDS one `ttk_affine_round_many` launch of these jobs (`tt_affine_rank_reduce_many`'s) declares --
+    the largest of the jobs' own requests -- or -1 when the batch cannot run as one launch: no job or more than
+    AFFINE_JOBS, or a job that does not fit one workgroup or passes the term limits."""
+    plan = _affine_many_plan(jobs)
+    if plan is None:
+        return -1
+    return int(D.lib.ttk_affine_round_many_lds(len(jobs), plan[2], None, None))
+
+
+def _affine_many_native(jobs):
+    """[(tt, tail factor or None, ||tt||^2)] from one `ttk_affine_round_many` launch -- one fresh buffer for every
+    job's output cores and one for the info block, one host read of the info block -- or None where that path is
+    not taken: the switch is off, there is no GPU, fewer than 2 or more than AFFINE_JOBS jobs, or a job without a
+    plan.  The callers' tensors are never written."""
+    if not (AFFINE_ROUND_MANY and D.DEV.type == "cuda") or len(jobs) < 2:
+        return None
+    plan = _affine_many_plan(jobs)
+    if plan is None:
+        return None
+    norm, plans, table = plan
+    nj = len(norm)
+    sizes, at = [], [0]
+    for (d, inner, _, _, _), sums, bound, _ in plans:
+        assert bound == retraction_ranks(inner, sums, [1 << 62] * (d - 1)), bound
+        sizes += [bound[k] * inner[k] * bound[k + 1] for k in range(d)]
+        at.append(len(sizes))
+    offs = np.concatenate(([0], np.cumsum([(s + 1) & ~1 for s in sizes])))  # 16-byte aligned cores
+    buf = D.empty(int(offs[-1]))
+    flat = [buf[int(o):int(o) + s] for o, s in zip(offs, sizes)]
+    ioff = (ctypes.c_int64 * (nj + 1))()
+    keep = []
+    for j in range(nj):
+        outs = flat[at[j]:at[j + 1]]
+        ptrs = (ctypes.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
+        keep.append(ptrs)
+        table[j].out = ctypes.cast(ptrs, ctypes.c_void_p)
+    if D.lib.ttk_affine_round_many_lds(nj, table, ioff, None) < 0:
+        return None
+    info = D.empty(int(ioff[nj]))
+    D._stream()
+    D.check(D.lib.ttk_affine_round_many(D.ctx(), nj, table, info.data_ptr()), "affine_round_many")
+    got = D.read(info)
+    res = []
+    for j, ((_, _, mode, mids), plan) in enumerate(zip(norm, plans)):
+        d, inner = plan[0][0], plan[0][1]
+        g = got[int(ioff[j]):int(ioff[j]) + d + 3]
+        q = [int(v) for v in g[:d + 1]]
+        tt = [o[:q[k] * inner[k] * q[k + 1]].view(q[k], *mids[k], q[k + 1])
+              for k, o in enumerate(flat[at[j]:at[j + 1]])]
+        res.append((tt, (pow(float(g[d + 1]), 1.0 / (2 * d)) if mode else None), float(g[d + 2])))
+    return res
+
+
+def tt_affine_rank_reduce_many(jobs):
+    """Several independent roundings of `tt_affine_rank_reduce`'s operand.  `jobs`: a list of (terms, eps, mode,
+    mids), `terms` and `mids` as there, mode 0 `tt_rank_reduce` / 1 the tracked rounding of `tt_psd_rank_reduce`
+    (at eps / 2, the discarded tail summed).  Returns one (tt, tail factor or None, ||tt||^2) per job, in order;
+    the tracked variant's correction (`_psd_correct`) is the caller's.  With TTIPM_AFFINE_ROUND_MANY=1, on the
+    GPU, for 2 to AFFINE_JOBS jobs every one of which has a plan (`affine_round_many_lds`): one launch with one
+    workgroup per job, one host read of every job's ranks, tail and squared norm, one output allocation
+    (`ttk_affine_round_many`), each job's bits those of its own `ttk_affine_round_one`.  Otherwise each job in
+    turn as `tt_affine_rank_reduce` runs it: `ttk_affine_round_one` where it is taken, else the composed path."""
+    jobs = list(jobs)
+    res = _affine_many_native(jobs)
+    if res is not None:
+        return res
+    res = []
+    for terms, eps, mode, mids in jobs:
+        one = _affine_native(terms, eps, mode, mids)
+        if one is None:
+            op = _affine_composed(*_affine_norm(terms, mids))
+            tt, factor = _tail_rank_reduce(op, eps) if mode else (tt_rank_reduce(op, eps), None)
+            one = (tt, factor, tt_inner_prod(tt, tt))
+        res.append(one)
+    return res
 
 
 def tt_fast_matrix_vec_mul(mat, vec, eps=1e-18):

@@ -50,6 +50,15 @@ against the one call `ttk_split_kick` (TTIPM_SPLIT_KICK=1).  Both paths draw the
 and upload it inside the clock.
 
     python tools/bench_round.py kick [reps] [rounds]
+
+`many` times a group of independent roundings as one launch (`ttk_affine_round_many`, one workgroup per job, one
+host read for the group: `tt_ops.tt_affine_rank_reduce_many` under TTIPM_AFFINE_ROUND_MANY=1) against the same
+jobs as N `ttk_affine_round_one` calls in sequence on the same library (one launch and one host read each), by the
+same method, at d = 10 with cores (r,2,2,R): 2, 3, 4 and 8 equal jobs (one plain train of ranks 8, 12 and 24 each,
+eps = 1e-2 of its norm), and a mixed group shaped like a Newton step's blocks, two symmetrisations
+0.5 M + 0.5 M^T and one plain train.  Every job's output bits are compared between the two paths.
+
+    python tools/bench_round.py many [reps] [rounds]
 """
 import hashlib
 import os
@@ -416,6 +425,84 @@ def main_affine(argv):
         bench_affine(update, 10, reps, rounds)
 
 
+def bench_many(name, jobs, reps, rounds):
+    """jobs: `tt_affine_rank_reduce_many`'s"""
+    def switches(many):
+        T.ROUND_ONE = T.PROD_ROUND_ONE = T.SUM_ROUND_ONE = False
+        T.AFFINE_ROUND_ONE, T.AFFINE_ROUND_MANY = True, many
+
+    def sequence():
+        switches(False)
+        return [T.tt_affine_rank_reduce(t, e, True, m) for t, e, _, m in jobs]
+
+    def batch():
+        switches(True)
+        return [(tt, n2) for tt, _, n2 in T.tt_affine_rank_reduce_many(jobs)]
+
+    lds = T.affine_round_many_lds(jobs)
+    assert lds >= 0
+    what = ((f"{len(jobs)} x ttk_affine_round_one", sequence), ("ttk_affine_round_many", batch))
+    info, outs = {}, {}
+    for label, f in what:
+        outs[label] = f()
+        torch.cuda.synchronize()
+        l0, s0 = D.lib.ttk_launch_count(), D.lib.ttk_sync_count()
+        f()
+        torch.cuda.synchronize()
+        info[label] = (D.lib.ttk_launch_count() - l0, D.lib.ttk_sync_count() - s0)
+        for _ in range(20):  # warm-up of every shape the timed window uses
+            f()
+    (seq, bat) = (outs[label] for label, _ in what)
+    same = all(n1 == n2 and len(a) == len(b) and all(torch.equal(x, y) for x, y in zip(a, b))
+               for (a, n1), (b, n2) in zip(seq, bat))
+    torch.cuda.synchronize()
+    times = {label: [] for label, _ in what}
+    for _ in range(rounds):
+        for label, f in what:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                f()
+            torch.cuda.synchronize()
+            times[label].append((time.perf_counter() - t0) / reps * 1e6)
+    T.AFFINE_ROUND_ONE = T.AFFINE_ROUND_MANY = False
+    print(f"d=10 {name}; LDS {lds} bytes; {reps} groups x {rounds} rounds, us per group; ranks out "
+          f"{[max(T.tt_ranks(tt)) for tt, _ in bat]}; bits of the two paths {'equal' if same else 'DIFFER'}",
+          flush=True)
+    for label, _ in what:
+        t = np.array(times[label])
+        nl, ns = info[label]
+        print(f"{label:28s} median {np.median(t):8.1f}  min {t.min():8.1f}  max {t.max():8.1f}  launches {nl:3d}  "
+              f"host waits {ns:2d}", flush=True)
+    old, new = (np.array(times[label]) for label, _ in what)
+    spread = max(old.max() - old.min(), new.max() - new.min())
+    gap = float(np.median(old) - np.median(new))
+    print(f"ttk_affine_round_many: {np.median(old) / np.median(new):.2f}x the sequence (medians {gap:.1f} us apart, "
+          f"min-max spread {spread:.1f} us: {'beyond' if abs(gap) > spread else 'within'} the spread); "
+          f"{np.median(new) / (np.median(old) / len(jobs)):.2f}x one member's time\n", flush=True)
+
+
+def main_many(argv):
+    reps = int(argv[0]) if argv else 100
+    rounds = int(argv[1]) if len(argv) > 1 else 7
+    assert torch.cuda.is_available(), "bench_round needs an MI355X"
+    rng = np.random.default_rng(5)
+    for r in (8, 12, 24):
+        ranks = [1] + [r] * 9 + [1]
+        trains = [train(rng, ranks) for _ in range(8)]
+        for n in (2, 3, 4, 8):
+            jobs = [([(1.0, t)], 1e-2 * T.tt_norm(t), 0, None) for t in trains[:n]]
+            bench_many(f"{n} equal jobs: one plain train of ranks {r} each, cores (r,2,2,R), eps 1e-2 |T|", jobs, reps,
+                       rounds)
+    for r in (4, 6, 12):
+        ranks = [1] + [r] * 9 + [1]
+        M1, M2, Y = train(rng, ranks), train(rng, ranks), train(rng, ranks)
+        jobs = [([(0.5, M), (0.5, M, True)], 1e-2 * T.tt_norm(M), 0, None) for M in (M1, M2)]
+        jobs.append(([(1.0, Y)], 1e-2 * T.tt_norm(Y), 0, None))
+        bench_many(f"mixed group: 2 x (0.5 M + 0.5 M^T) at term ranks {r}+{r} and one plain train of ranks {r}", jobs,
+                   reps, rounds)
+
+
 def bench_kick(a, b, r, bwd, reps, rounds):
     from ttipm_amd import tt_eig as E
     rng = np.random.default_rng(5)
@@ -485,6 +572,8 @@ def main_kick(argv):
 if __name__ == "__main__":
     if sys.argv[1:2] == ["kick"]:
         main_kick(sys.argv[2:])
+    elif sys.argv[1:2] == ["many"]:
+        main_many(sys.argv[2:])
     elif sys.argv[1:2] == ["affine"]:
         main_affine(sys.argv[2:])
     elif sys.argv[1:2] == ["prod"]:
