@@ -625,6 +625,8 @@ int ttk_round_one(ttk_ctx ctx, int d, const double *const *cores, const int64_t 
  * axis, each times its weight, core d-1 the terms stacked along the first axis, an interior core block
  * diagonal, everything else exactly 0.0 (`tt_add`'s layout).  The kernel's two loads write these cores
  * straight into LDS, every element once by the thread that owns it; they never exist in global memory.
+ * The call is ttk_affine_round_one's operand with plain terms only (kind -1), planned, checked and launched
+ * by the same code; only the size of info differs.
  * coef_j is applied once, to the term's core 0, as one rounded product; a weight of exactly 1.0 copies
  * the bits.  op_j is the identity (transpose 0) or the swap of the two middle indices (transpose 1):
  * rows[k] is the first middle extent n1_k of S's core k, n2_k = inner[k] / rows[k], a transposed term
@@ -636,6 +638,7 @@ int ttk_round_one(ttk_ctx ctx, int d, const double *const *cores, const int64_t 
  * ttk_sum_term: cores, d device pointers to contiguous (ranks[k], inner[k], ranks[k+1]) fp64 cores (a
  * transposed term: (ranks[k], n2_k, n1_k, ranks[k+1])); ranks, d+1 entries, ranks[0] == ranks[d] == 1;
  * coef finite; transpose 0 or 1.  out[k]: bound[k] inner[k] bound[k+1] doubles that overlap no input.
+ * info: d + 2 doubles, ttk_round_one's; nothing behind them is written.
  * ttk_sum_round_one_lds: the bytes of LDS, or -1 when the sum does not fit one workgroup (at most
  * 160 KiB and 32 cores) or the arguments are invalid -- the caller then builds the sum and takes
  * ttk_round; it fills sum_ranks and bound (d+1 entries each) unless NULL.  ttk_sum_round_one validates
@@ -671,9 +674,11 @@ int ttk_sum_round_one(ttk_ctx ctx, int d, const int64_t *inner, const int64_t *r
  * may alias each other (x o x); the inputs are read only.  Everything after the loads is ttk_round_one on
  * P: the plan (LDS bytes, thread count, bound ranks) is ttk_round_one_lds(d, mid, R), the same rank rule,
  * eps, mode, out and info, one launch, no host read, and the bits of ttk_round_one on a materialised P that
- * holds the same numbers.
+ * holds the same numbers.  The call is ttk_affine_round_one's operand with this one product term, weight
+ * exactly 1.0 and not transposed, planned, checked and launched by the same code; only the size of info differs.
  * a[k], b[k]: device pointers to the contiguous fp64 cores above; a_ranks, b_ranks: d+1 entries each, the
- * boundary ranks 1.  out[k]: bound[k] mid_k bound[k+1] doubles that overlap no input; info: d + 2 doubles.
+ * boundary ranks 1.  out[k]: bound[k] mid_k bound[k+1] doubles that overlap no input; info: d + 2 doubles,
+ * ttk_round_one's; nothing behind them is written.
  * ttk_prod_round_one_lds: the bytes of LDS, or -1 when the product does not fit one workgroup (at most
  * 160 KiB and 32 cores; a rank, an extent or a product of two above the LDS capacity) or the arguments are
  * invalid -- the caller then takes ttk_zipup; it fills prod_ranks and bound (d+1 entries each) unless
@@ -706,10 +711,11 @@ int ttk_prod_round_one(ttk_ctx ctx, int kind, int d, const double *const *a, con
  * Arithmetic: each LDS element is written once by the thread that owns it.  A plain element is loaded; a
  * product element is ttk_prod_round_one's (kinds 2, 3: one rounded multiply; kinds 0, 1: the rounded
  * product at c = 0, then fma with c ascending); coef_j multiplies the finished element of core 0 once,
- * rounded, and a coef of exactly 1.0 copies the bits.  Hence the bits of ttk_sum_round_one for plain terms
- * only, of ttk_prod_round_one for one untransposed product with coef 1.0, and of ttk_round_one on a
- * materialised S that holds the same numbers.  Everything after the loads is ttk_round_one on S: the plan is
- * ttk_round_one_lds(d, inner, sum_ranks), the same rank rule, eps, mode and out.
+ * rounded, and a coef of exactly 1.0 copies the bits.  ttk_sum_round_one (plain terms only) and
+ * ttk_prod_round_one (one untransposed product with coef 1.0) are this operand through this code, so their
+ * bits are these; and the bits are those of ttk_round_one on a materialised S that holds the same numbers.
+ * Everything after the loads is ttk_round_one on S: the plan is ttk_round_one_lds(d, inner, sum_ranks), the
+ * same rank rule, eps, mode and out.
  * info: d + 3 doubles.  info[0 .. d] the ranks, info[d+1] the discarded tail (mode 1, else 0.0), as
  * ttk_round_one; info[d+2] = ||result||^2, the sum of squares of the last output core (the others have
  * orthonormal columns), reduced in a fixed order, so two calls give the same bits.

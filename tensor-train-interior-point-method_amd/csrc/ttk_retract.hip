@@ -34,26 +34,23 @@
 // are planned from the bound ranks (no upper bound), which the run-time ranks can only undercut.  The
 // ranks and the discarded tail go to `info` on the device; the call itself reads nothing back.
 //
-// `ttk_sum_round_one` is `ttk_round_one` on the weighted sum S = sum_j c_j op_j(T_j) of up to RS_TERMS trains
-// (`tt_add` of `tt_scale`d and transposed trains, cy_src/tt_ops_cy.pyx:94-114, :243-258) that is never built:
-// the kernel reads its input cores in exactly two places, and there the summed core -- term j's block at the
-// prefix-sum offsets of its ranks, times c_j in core 0, its two middle indices swapped where asked, exactly 0.0
-// elsewhere -- is written straight into the LDS region the plain load fills, each element once by the thread
-// that owns it (rt_load_core).  The plan is the one of the summed ranks; everything after the loads is
-// retract_kernel<true, RtPlan>'s code.
-//
-// `ttk_prod_round_one` is `ttk_round_one` on the core-wise product of two trains (`tt_fast_matrix_vec_mul`,
-// `tt_fast_mat_mat_mul`, `tt_fast_hadamard` as the device path computes them, DESIGN.md §3.1: Kronecker bonds,
-// rounded once at eps) that is never built either: the same two loads write core k of the product, row a r_b + b,
-// column A R_b + B, each element one multiply or a short fma chain over the contracted index of two small cores
-// read from global memory.  The plan is the one of the product ranks.
-//
-// `ttk_affine_round_one` closes the family: S = sum_j c_j op_j(T_j) of up to RS_TERMS terms, each a plain train
-// or the core-wise product of two (at most RA_PRODS of them), in `tt_add`'s block layout at the prefix sums of
-// the term ranks.  Its loader finds the owning term as the sum's does and computes the element with the
-// functions the two loaders above share, so a sum of plain terms or a single product gives their bits.  It
-// alone also leaves ||result||^2 in info[d + 2]: after phase B every output core but the last has orthonormal
+// `ttk_affine_round_one` is `ttk_round_one` on an operand that is never built: S = sum_j c_j op_j(T_j) of up to
+// RS_TERMS terms, each a plain train or the core-wise product of two (at most RA_PRODS of them), in `tt_add`'s
+// block layout at the prefix sums of the term ranks (cy_src/tt_ops_cy.pyx:94-114, :243-258).  The kernel reads
+// its input cores in exactly two places, and there the core of S -- term j's block, times c_j in core 0, its two
+// middle indices swapped where asked, exactly 0.0 elsewhere -- is written straight into the LDS region the plain
+// load fills, each element once by the thread that owns it (rt_load_core on RtAffineArg).  A product term is the
+// device path's `tt_fast_matrix_vec_mul`, `tt_fast_mat_mat_mul` or `tt_fast_hadamard` before its rounding
+// (Kronecker bonds), row a r_b + b, column A R_b + B, each element one multiply or a short fma
+// chain over the contracted index of two small cores read from global memory.  The plan is the one of the summed
+// ranks; everything after the loads is retract_kernel<true, RtPlan>'s code.  With the plan's RT_NORM2 bit the
+// kernel also leaves ||result||^2 in info[d + 2]: after phase B every output core but the last has orthonormal
 // columns, so that is the sum of squares of the last carried core, reduced by wave 0 in a fixed order.
+//
+// `ttk_sum_round_one` (plain terms only) and `ttk_prod_round_one` (one product, weight exactly 1.0, not
+// transposed) are that operand and that kernel: their entry points translate their arguments into terms, plan
+// and launch through the same code, and clear RT_NORM2, since their info has d + 2 words.  A sum of plain terms
+// or a single product given to `ttk_affine_round_one` therefore has their bits by construction.
 //
 // `ttk_affine_round_many` runs up to TTK_ROUND_MANY_MAX of these roundings in one launch, workgroup j on job j
 // (retract_many_kernel).  The body is the same function (retract_body); the jobs' RtAffineArg records lie in a
@@ -84,46 +81,26 @@ struct RtPlan {
   int so[TT_MAXD];       // orthogonalised core k's offset in the scratch block (doubles), k = 1 .. d-1
   int oP0, oP1, oC, oG, oM, oT, oS;  // LDS regions (offsets in doubles, all even: 16-byte aligned)
   int oQ;                // ttk_round_one: the run-time ranks q_0 .. q_{d-1} as doubles (each one published once)
-  int track;             // ttk_round_one: mode 1, the discarded tail sums are accumulated
+  int track;             // ttk_round_one: RT_TRACK | RT_NORM2, uniform across the workgroup
   double thr2;           // ttk_round_one: the squared per-bond threshold
-  double *info;          // ttk_round_one: d + 2 device doubles, the ranks and the tail
+  double *info;          // ttk_round_one: d + 2 device doubles, the ranks and the tail (RT_NORM2: d + 3)
   const double *core[TT_MAXD];
   double *out[TT_MAXD];
 };
 
-constexpr int RS_TERMS = 4;  // terms of a summed train
+constexpr int RT_TRACK = 1;  // mode 1: the discarded tail sums are accumulated
+constexpr int RT_NORM2 = 2;  // ||result||^2 goes to info[d + 2] (the affine entries; the others own d + 2 words)
 
-// `ttk_sum_round_one`: the plan of the summed train S (p.r its ranks, p.core unused) and the terms.
-struct RtSumArg {
-  RtPlan p;
-  int nterms;
-  int tr[RS_TERMS];             // 1: the term stores core k as (r, n2_k, n1_k, r')
-  int n1[TT_MAXD];              // first middle extent of S's core k (n_k where no term is transposed)
-  int r[RS_TERMS][TT_MAXD + 1]; // the terms' bond ranks
-  double coef[RS_TERMS];        // applied to the term's core 0
-  const double *core[RS_TERMS][TT_MAXD];
-};
-static_assert(sizeof(RtSumArg) < 4096, "the plan and the terms travel as one kernel argument");
+constexpr int RS_TERMS = 4;  // terms of an operand
+constexpr int RA_PRODS = 2;  // product terms among them
 
-// `ttk_prod_round_one`: the plan of the product train (p.r = ra rb, p.n the product's middle extents, p.core
-// unused) and the two factors.  Core k of a is (ra_k, m0_k, m1_k, ra_{k+1}); of b (rb_k, m1_k, m2_k, rb_{k+1})
-// where the products contract m1 (kind 0 with m2 = 1, kind 1), (rb_k, m0_k m1_k, rb_{k+1}) where they multiply
-// elementwise (kind 2 with m1 = 1, kind 3).  An extent the kind does not use is stored as 1.
-struct RtProdArg {
-  RtPlan p;
-  int kind;
-  int ra[TT_MAXD + 1], rb[TT_MAXD + 1];        // the factors' bond ranks
-  int m0[TT_MAXD], m1[TT_MAXD], m2[TT_MAXD];   // the physical extents of core k
-  const double *a[TT_MAXD];
-  const double *b[TT_MAXD];
-};
-static_assert(sizeof(RtProdArg) < 4096, "the plan and the factors travel as one kernel argument");
-
-constexpr int RA_PRODS = 2;  // product terms of an affine operand
-
-// `ttk_affine_round_one`: the plan of S (p.r the summed ranks, p.core unused) and the terms.  Term j is the train
-// a[j] (kind -1) or the product of a[j] and b[slot[j]] (kinds 0 .. 3, RtProdArg's extents per slot).  Ranks and
-// extents are 16-bit (TT_CAP fits) so that four terms, two of them products, travel as one kernel argument.
+// The operand of every rounding of a train that is never built (`ttk_sum_round_one`, `ttk_prod_round_one`,
+// `ttk_affine_round_one` and `_many`): the plan of S (p.r the summed ranks, p.core unused) and the terms.  Term j
+// is the train a[j] (kind -1) or the product of a[j] and b[slot[j]] (kinds 0 .. 3).  Per product slot: core k of a
+// is (ra_k, m0_k, m1_k, ra_{k+1}); of b (rb_k, m1_k, m2_k, rb_{k+1}) where the products contract m1 (kind 0 with
+// m2 = 1, kind 1), (rb_k, m0_k m1_k, rb_{k+1}) where they multiply elementwise (kind 2 with m1 = 1, kind 3); an
+// extent the kind does not use is stored as 1.  Ranks and extents are 16-bit (TT_CAP fits) so that four terms,
+// two of them products, travel as one kernel argument.
 struct RtAffineArg {
   RtPlan p;
   int nterms;
@@ -229,17 +206,15 @@ __device__ int rt_kept_rank(const double *sv, const int *perm, int pp, double th
 }
 
 __device__ __forceinline__ const RtPlan &rt_plan_of(const RtPlan &a) { return a; }
-__device__ __forceinline__ const RtPlan &rt_plan_of(const RtSumArg &a) { return a.p; }
-__device__ __forceinline__ const RtPlan &rt_plan_of(const RtProdArg &a) { return a.p; }
 __device__ __forceinline__ const RtPlan &rt_plan_of(const RtAffineArg &a) { return a.p; }
 
 // Core k of the train, (r_k, n_k, r_{k+1}) row-major, into dst.  No barrier: the caller's next one publishes it.
-// (tid, nt): the team, as in ttk_tt_gemm.h, here and in the three loaders below.
+// (tid, nt): the team, as in ttk_tt_gemm.h, here and in the operand's loader below.
 __device__ __forceinline__ void rt_load_core(double *dst, const RtPlan &a, int k, int tid, int nt) {
   ro_load(dst, a.core[k], a.r[k] * a.n[k] * a.r[k + 1], tid, nt);
 }
 
-// The element code the operand loaders share, so that equal operands give equal bits.
+// The element code of the operand's loader.
 // The term's own middle index of S's middle index i = i1 n2 + i2: i2 n1 + i1 where the term is transposed.
 __device__ __forceinline__ int rt_term_mid(bool tr, int i, int n1, int n2) {
   if (!tr) return i;
@@ -272,49 +247,12 @@ __device__ __forceinline__ double rt_prod_elem(bool contract, const double *__re
   return __dmul_rn(pa[(a * n + mid) * Ra + A], pb[(b * n + mid) * Rb + B]);
 }
 
-// Core k of the summed train: element (a, i, b) belongs to the one term whose row range holds a (every term
-// at k = 0, where R_0 = 1) and whose column range holds b (every term at k = d-1), and is 0.0 if there is
-// none.  Each destination element is written once, by the thread that owns it.
-__device__ __forceinline__ void rt_load_core(double *dst, const RtSumArg &s, int k, int tid, int nt) {
-  const int n = s.p.n[k], R1 = s.p.r[k + 1], nR1 = n * R1, total = s.p.r[k] * nR1;
-  const int n1 = s.n1[k], n2 = n / n1;
-  const bool first = k == 0, last = k == s.p.d - 1;
-  for (int e = tid; e < total; e += nt) {
-    const int a = e / nR1, rem = e - a * nR1, i = rem / R1, b = rem - i * R1;
-    double v = 0.0;
-    int A = 0, B = 0;
-    for (int j = 0; j < s.nterms; ++j) {
-      const int ra = s.r[j][k], rb = s.r[j][k + 1];
-      const int la = first ? 0 : a - A, lb = last ? 0 : b - B;
-      if (la >= 0 && la < ra && lb >= 0 && lb < rb) {
-        const int mid = rt_term_mid(s.tr[j] != 0, i, n1, n2);
-        v = rt_weighted(first, s.coef[j], s.core[j][k][(la * n + mid) * rb + lb]);
-      }
-      A += ra, B += rb;
-    }
-    dst[e] = v;
-  }
-}
-
-// Core k of the product train: element (a rb + b, mid, A Rb + B) by rt_prod_elem.  Each destination element is
-// written once, by the thread that owns it.  kind and every extent are uniform across the workgroup.
-__device__ __forceinline__ void rt_load_core(double *dst, const RtProdArg &s, int k, int tid, int nt) {
-  const int rb = s.rb[k], Ra = s.ra[k + 1], Rb = s.rb[k + 1];
-  const int m0 = s.m0[k], m1 = s.m1[k], m2 = s.m2[k];
-  const int n = s.p.n[k], R1 = s.p.r[k + 1], nR1 = n * R1, total = s.p.r[k] * nR1;
-  const double *__restrict__ pa = s.a[k], *__restrict__ pb = s.b[k];
-  const bool contract = s.kind < 2;
-  for (int e = tid; e < total; e += nt) {
-    const int row = e / nR1, rem = e - row * nR1, mid = rem / R1, col = rem - mid * R1;
-    const int a = row / rb, b = row - a * rb, A = col / Rb, B = col - A * Rb;
-    dst[e] = rt_prod_elem(contract, pa, pb, a, b, mid, A, B, Ra, Rb, m0, m1, m2, n);
-  }
-}
-
-// Core k of the affine operand: the owning term as in the sum's loader, the term's middle index remapped first
-// where it is transposed, then the plain element loaded or the product element computed at that index, then
-// the weight.  Each destination element is written once, by the thread that owns it; the term tables are
-// kernel arguments (in the batched launch, the job's record) indexed by the uniform j and k.
+// Core k of the operand: element (row, i, col) belongs to the one term whose row range holds row (every term at
+// k = 0, where R_0 = 1) and whose column range holds col (every term at k = d-1), and is 0.0 if there is none.
+// The term's middle index is remapped first where it is transposed, then the plain element is loaded or the
+// product element (row a rb + b, column A Rb + B of the term) computed at that index, then the weight applied.
+// Each destination element is written once, by the thread that owns it; kind, the term tables and every
+// extent are kernel arguments (in the batched launch, the job's record) indexed by the uniform j and k.
 __device__ __forceinline__ void rt_load_core(double *dst, const RtAffineArg &s, int k, int tid, int nt) {
   const int n = s.p.n[k], R1 = s.p.r[k + 1], nR1 = n * R1, total = s.p.r[k] * nR1;
   const int n1 = s.n1[k], n2 = n / n1;
@@ -345,16 +283,11 @@ __device__ __forceinline__ void rt_load_core(double *dst, const RtAffineArg &s, 
   }
 }
 
-// Whether the operand's kernel leaves the squared norm of the result in info[d + 2]: a compile-time property
-// of the argument type, so the other instantiations keep their code.
-template <class Arg> struct RtNorm2 { static constexpr bool value = false; };
-template <> struct RtNorm2<RtAffineArg> { static constexpr bool value = true; };
-
 // ADAPT false: `ttk_retract`, every q_i from the plan.  ADAPT true: `ttk_round_one`, p.q holds the bounds and
-// q_{i+1} is decided after bond i's Jacobi.  Arg: RtPlan, the cores as they lie in global memory, or RtSumArg,
-// the cores of the summed train (`ttk_sum_round_one`), or RtProdArg, the cores of the product train
-// (`ttk_prod_round_one`), or RtAffineArg, the cores of a weighted sum of trains and products
-// (`ttk_affine_round_one`); it only enters the two rt_load_core calls and, for RtAffineArg, adds info[d + 2].
+// q_{i+1} is decided after bond i's Jacobi.  Arg: RtPlan, the cores as they lie in global memory, or RtAffineArg,
+// the cores of a weighted sum of trains and products (`ttk_sum_round_one`, `ttk_prod_round_one`,
+// `ttk_affine_round_one`); it only enters the two rt_load_core calls.  Whether info[d + 2] is written is the
+// plan's RT_NORM2 bit, read at run time: the sum and product entries own d + 2 words of info and leave it clear.
 //
 // The body is one function for the single-call kernel and the batched one (retract_many_kernel).  (tid, nt) is
 // the team of ttk_tt_gemm.h: the single-call kernels pass (threadIdx.x, blockDim.x) with blockDim.x == p.nt; the
@@ -407,7 +340,7 @@ __device__ __forceinline__ void retract_body(const Arg &arg, double *scr, const 
     const int *perm = tt_jacobi_svd(A, G, sv, pp, n, tid, nt);
     int qn = p.q[i + 1];
     if (ADAPT) {  // one thread decides, one barrier publishes: qn is uniform and 1 <= qn <= pp <= p.q[i + 1]
-      if (tid == 0) qd[i + 1] = (double)rt_kept_rank(sv, perm, pp, p.thr2, p.track != 0, &tail);
+      if (tid == 0) qd[i + 1] = (double)rt_kept_rank(sv, perm, pp, p.thr2, (p.track & RT_TRACK) != 0, &tail);
       __syncthreads();
       qn = (int)qd[i + 1];
     }
@@ -443,7 +376,7 @@ __device__ __forceinline__ void retract_body(const Arg &arg, double *scr, const 
     p.info[d] = 1.0;
     p.info[d + 1] = tail;
   }
-  if (RtNorm2<Arg>::value) {
+  if (ADAPT && (p.track & RT_NORM2)) {
     // ||result||^2 = the sum of squares of the last carried core (published by the loop's last barrier): wave 0
     // alone, lane l the elements l, l + 64, ... ascending, then the fixed wave tree
     if (tid < 64) {
@@ -479,45 +412,9 @@ __global__ __launch_bounds__(1024) void retract_many_kernel(const RtManyJob *__r
   retract_body<true>(job.a, scr + job.scr, (int)threadIdx.x < nt ? (int)threadIdx.x : TT_IDLE, nt);
 }
 
-// `ttk_sum_round_one`'s checks on the terms and the plan of the summed train: the bytes of dynamic LDS, -1 when
-// the sum does not fit one workgroup, -2 on invalid arguments.  sum: the summed ranks, d + 1 entries.
-int64_t rs_plan(int d, const int64_t *inner, int nterms, const ttk_sum_term *terms, RtSumArg *a, int64_t *words,
-                int64_t *sum) {
-  if (nterms < 1 || nterms > RS_TERMS || !terms) return -2;
-  bool big = false;
-  for (int j = 0; j < nterms; ++j) {
-    const ttk_sum_term &t = terms[j];
-    if (!t.cores || !std::isfinite(t.coef) || (t.transpose != 0 && t.transpose != 1)) return -2;
-    const int chk = tt_check_extents(d, inner, {t.ranks});
-    if (chk == -2 || t.ranks[0] != 1 || t.ranks[d] != 1) return -2;
-    big |= chk != 0;
-  }
-  if (big) return -1;  // d <= TT_MAXD and every rank <= TT_CAP from here on
-  for (int j = 0; j < nterms; ++j)
-    for (int k = 0; k < d; ++k)
-      if (!terms[j].cores[k]) return -2;
-  sum[0] = sum[d] = 1;
-  for (int k = 1; k < d; ++k) {
-    sum[k] = 0;
-    for (int j = 0; j < nterms; ++j) sum[k] += terms[j].ranks[k];
-  }
-  const int64_t shm = rt_plan(d, inner, sum, nullptr, true, &a->p, words);
-  if (shm < 0) return shm;
-  a->nterms = nterms;
-  for (int j = 0; j < RS_TERMS; ++j) {
-    const bool on = j < nterms;
-    a->tr[j] = on ? terms[j].transpose : 0;
-    a->coef[j] = on ? terms[j].coef : 0.0;
-    for (int k = 0; k <= d; ++k) a->r[j][k] = on ? (int)terms[j].ranks[k] : 0;
-    for (int k = 0; k < d; ++k) a->core[j][k] = on ? terms[j].cores[k] : nullptr;
-  }
-  for (int k = 0; k < d; ++k) a->n1[k] = (int)inner[k], a->p.core[k] = nullptr;
-  return shm;
-}
-
-// The checks on the two factors of a product that `ttk_prod_round_one` and `ttk_affine_round_one` share: -2 on
-// invalid arguments, -1 when a rank, an extent or a product of two passes TT_CAP or d passes TT_MAXD, else 0
-// with inner[k] the product's middle extents and m[3k ..] the physical extents (1 where the kind has none).
+// The checks on the two factors of a product term (`ttk_prod_round_one`'s, which takes its middle extents from
+// here, and those of `ttk_affine_round_one`): -2 on invalid arguments, -1 when a rank, an extent or a product of
+// two passes TT_CAP or d passes TT_MAXD, else 0 with inner[k] the product's middle extents and m[3k ..] the physical extents (1 where the kind has none).
 int rp_check(int kind, int d, const int64_t *a_ranks, const int64_t *b_ranks, const int64_t *modes, int64_t *inner,
              int *m) {
   if (kind < 0 || kind > 3 || d < 2 || !a_ranks || !b_ranks || !modes) return -2;
@@ -542,29 +439,11 @@ int rp_check(int kind, int d, const int64_t *a_ranks, const int64_t *b_ranks, co
   return 0;
 }
 
-// `ttk_prod_round_one`'s checks on the factors and the plan of the product train: the bytes of dynamic LDS, -1
-// when the product does not fit one workgroup, -2 on invalid arguments.  prod: the product ranks, d + 1 entries.
-int64_t rp_plan(int kind, int d, const int64_t *a_ranks, const int64_t *b_ranks, const int64_t *modes, RtProdArg *a,
-                int64_t *words, int64_t *prod) {
-  int64_t inner[TT_MAXD];
-  int m[3 * TT_MAXD];
-  if (const int chk = rp_check(kind, d, a_ranks, b_ranks, modes, inner, m)) return chk;
-  for (int k = 0; k < d; ++k) a->m0[k] = m[3 * k], a->m1[k] = m[3 * k + 1], a->m2[k] = m[3 * k + 2];
-  for (int k = 0; k <= d; ++k) {
-    prod[k] = a_ranks[k] * b_ranks[k];
-    a->ra[k] = (int)a_ranks[k], a->rb[k] = (int)b_ranks[k];
-  }
-  const int64_t shm = rt_plan(d, inner, prod, nullptr, true, &a->p, words);
-  if (shm < 0) return shm;
-  a->kind = kind;
-  for (int k = 0; k < d; ++k) a->a[k] = a->b[k] = a->p.core[k] = nullptr;
-  return shm;
-}
-
-// `ttk_affine_round_one`'s checks on the terms and the plan of S: the bytes of dynamic LDS, -1 when S does not fit
-// one workgroup, -2 on invalid arguments or more than RS_TERMS terms or RA_PRODS products.  sum: the summed
-// ranks, d + 1 entries.
-int64_t ra_plan(int d, const int64_t *inner, int nterms, const ttk_affine_term *terms, RtAffineArg *a,
+// The checks on the terms of an operand and the plan of S: the bytes of dynamic LDS, -1 when S does not fit one
+// workgroup, -2 on invalid arguments or more than RS_TERMS terms or RA_PRODS products.  sum: the summed ranks,
+// d + 1 entries.  ptrs false (`ttk_prod_round_one_lds`, which is given no cores): the core tables a and b are
+// neither examined nor copied.
+int64_t ra_plan(int d, const int64_t *inner, int nterms, const ttk_affine_term *terms, bool ptrs, RtAffineArg *a,
                 int64_t *words, int64_t *sum) {
   if (nterms < 1 || nterms > RS_TERMS || !terms) return -2;
   if (tt_check_extents(d, inner, {}) == -2) return -2;
@@ -577,7 +456,7 @@ int64_t ra_plan(int d, const int64_t *inner, int nterms, const ttk_affine_term *
   nprod = 0;
   for (int j = 0; j < nterms; ++j) {
     const ttk_affine_term &t = terms[j];
-    if (t.kind < -1 || t.kind > 3 || !t.a || !t.a_ranks || !std::isfinite(t.coef) ||
+    if (t.kind < -1 || t.kind > 3 || (ptrs && !t.a) || !t.a_ranks || !std::isfinite(t.coef) ||
         (t.transpose != 0 && t.transpose != 1))
       return -2;
     if (t.kind < 0) {
@@ -586,7 +465,7 @@ int64_t ra_plan(int d, const int64_t *inner, int nterms, const ttk_affine_term *
       if (chk == -2 || t.a_ranks[0] != 1 || t.a_ranks[d] != 1) return -2;
       big |= chk != 0;
     } else {
-      if (!t.b) return -2;
+      if (ptrs && !t.b) return -2;
       const int chk = rp_check(t.kind, d, t.a_ranks, t.b_ranks, t.modes, mid, m[nprod++]);
       if (chk == -2) return -2;
       big |= chk != 0;
@@ -595,7 +474,7 @@ int64_t ra_plan(int d, const int64_t *inner, int nterms, const ttk_affine_term *
     }
   }
   if (big || tt_check_extents(d, inner, {}) != 0) return -1;  // d <= TT_MAXD, ranks and extents <= TT_CAP from here on
-  for (int j = 0; j < nterms; ++j)
+  for (int j = 0; ptrs && j < nterms; ++j)
     for (int k = 0; k < d; ++k)
       if (!terms[j].a[k] || (terms[j].kind >= 0 && !terms[j].b[k])) return -2;
   sum[0] = sum[d] = 1;
@@ -626,9 +505,9 @@ int64_t ra_plan(int d, const int64_t *inner, int nterms, const ttk_affine_term *
       if (prod) a->ra[t][k] = (unsigned short)ra, a->rb[t][k] = (unsigned short)rb;
     }
     for (int k = 0; k < d; ++k) {
-      a->a[j][k] = on ? terms[j].a[k] : nullptr;
+      a->a[j][k] = on && ptrs ? terms[j].a[k] : nullptr;
       if (prod) {
-        a->b[t][k] = terms[j].b[k];
+        a->b[t][k] = ptrs ? terms[j].b[k] : nullptr;
         a->m0[t][k] = (unsigned short)m[t][3 * k], a->m1[t][k] = (unsigned short)m[t][3 * k + 1];
         a->m2[t][k] = (unsigned short)m[t][3 * k + 2];
       }
@@ -638,27 +517,50 @@ int64_t ra_plan(int d, const int64_t *inner, int nterms, const ttk_affine_term *
   return shm;
 }
 
-// Every check of `ttk_affine_round_one` on one operand, for it and for each job of `ttk_affine_round_many`, and
-// the finished kernel argument (plan, terms, rows, threshold, mode, out, info).  who: the name the message starts
-// with, or null for the planners, which set none.  outs: whether out and info are examined.  Returns TTK_OK with
-// *shm and *words set, else TTK_ERR_ARG.
-int ra_prepare(const char *who, int d, const int64_t *inner, const int64_t *rows, int nterms,
-               const ttk_affine_term *terms, double eps, int mode, bool outs, double *const *out, double *info,
-               RtAffineArg *a, int64_t *words, int64_t *shm) {
+// The three `_lds` planners: ra_plan's bytes of LDS, -1 for both of its failures, with the summed (product) ranks
+// and the bound ranks, d + 1 entries each, where the caller asks for them.
+int64_t ra_lds(int d, const int64_t *inner, int nterms, const ttk_affine_term *terms, bool ptrs, int64_t *sum_ranks,
+               int64_t *bound) {
+  RtAffineArg a;
+  int64_t words, sum[TT_MAXD + 1];
+  const int64_t b = ra_plan(d, inner, nterms, terms, ptrs, &a, &words, sum);
+  if (b < 0) return -1;
+  for (int k = 0; sum_ranks && k <= d; ++k) sum_ranks[k] = sum[k];
+  for (int k = 0; bound && k <= d; ++k) bound[k] = a.p.q[k];
+  return b;
+}
+
+// What each entry's bad-arguments message lists: only the rules its own caller can break.
+const char RS_RULES[] =
+    "d >= 2, 1 to 4 terms, every rank and extent >= 1, boundary ranks 1, no null pointer, coef finite, transpose 0 "
+    "or 1, eps finite and >= 0, mode 0 or 1";
+const char RP_RULES[] =
+    "kind 0 to 3, d >= 2, every rank and extent >= 1, boundary ranks 1, no null pointer, eps finite and >= 0, mode "
+    "0 or 1";
+const char RA_RULES[] =
+    "d >= 2, 1 to 4 terms, at most 2 of them products, kind -1 to 3, b, b_ranks and modes null exactly for kind -1, "
+    "every rank and extent >= 1, boundary ranks 1, a product's middle extent equal to inner, no null pointer, coef "
+    "finite, transpose 0 or 1, eps finite and >= 0, mode 0 or 1";
+
+// A failed plan (-2 invalid, -1 no fit) as the entry's error.  who: the name the message starts with, or null for
+// the planners, which set none.
+int ra_fail(const char *who, const char *rules, int64_t shm) {
+  if (who && shm == -2) ttk::set_error("%s: bad arguments (%s)", who, rules);
+  if (who && shm != -2) ttk::set_error("%s: the operand does not fit one workgroup's LDS (its _lds gives -1)", who);
+  return TTK_ERR_ARG;
+}
+
+// Every check of the three entries on one operand, also for each job of `ttk_affine_round_many`, and the finished
+// kernel argument (plan, terms, rows, threshold, mode, out, info).  who, rules: ra_fail's.  outs: whether out and
+// info are examined.  norm2: info has d + 3 words and the last takes ||result||^2.  Returns TTK_OK with *shm and
+// *words set, else TTK_ERR_ARG.
+int ra_prepare(const char *who, const char *rules, int d, const int64_t *inner, const int64_t *rows, int nterms,
+               const ttk_affine_term *terms, double eps, int mode, bool outs, bool norm2, double *const *out,
+               double *info, RtAffineArg *a, int64_t *words, int64_t *shm) {
   int64_t sum[TT_MAXD + 1];
   const bool ok = (!outs || (out && info)) && eps >= 0.0 && eps <= 1.79769313486231570e308 && (mode == 0 || mode == 1);
-  *shm = ok ? ra_plan(d, inner, nterms, terms, a, words, sum) : -2;
-  if (*shm < 0) {
-    if (who)
-      ttk::set_error(*shm == -2
-                         ? "%s: bad arguments (d >= 2, 1 to 4 terms, at most 2 of them products, kind -1 to 3, b, "
-                           "b_ranks and modes null exactly for kind -1, every rank and extent >= 1, boundary ranks 1, "
-                           "a product's middle extent equal to inner, no null pointer, coef finite, transpose 0 or 1, "
-                           "eps finite and >= 0, mode 0 or 1)"
-                         : "%s: the operand does not fit one workgroup's LDS (ttk_affine_round_one_lds)",
-                     who);
-    return TTK_ERR_ARG;
-  }
+  *shm = ok ? ra_plan(d, inner, nterms, terms, true, a, words, sum) : -2;
+  if (*shm < 0) return ra_fail(who, rules, *shm);
   bool transposed = false;
   for (int j = 0; j < nterms; ++j) transposed |= terms[j].transpose != 0;
   if (transposed && !rows) {
@@ -679,9 +581,37 @@ int ra_prepare(const char *who, int d, const int64_t *inner, const int64_t *rows
   }
   const double e = (mode ? eps / 2.0 : eps) / std::sqrt((double)(d - 1));
   a->p.thr2 = e * e;
-  a->p.track = mode;
+  a->p.track = (mode ? RT_TRACK : 0) | (norm2 ? RT_NORM2 : 0);
   a->p.info = info;
   return TTK_OK;
+}
+
+// One launch of the operand's kernel on the context's stream: `ttk_sum_round_one`, `ttk_prod_round_one` and
+// `ttk_affine_round_one` after ra_prepare.
+int ra_launch(const RtAffineArg &a, int64_t words, int64_t shm) {
+  TtScratch w(ttk::ctx().stream);  // the orthogonalised cores 1 .. d-1
+  TTK_HIP(w.alloc(words));
+  tt_lds_attr(retract_kernel<true, RtAffineArg>, shm);
+  hipLaunchKernelGGL((retract_kernel<true, RtAffineArg>), dim3(1), dim3(a.p.nt), (size_t)shm, w.st, a, w.get());
+  TTK_LAUNCH_CHECK();
+  return TTK_OK;
+}
+
+// `ttk_sum_round_one`'s terms as plain terms of the operand (kind -1: the train, its weight and transposition as
+// given), in t; null when there is no table.  nterms is ra_plan's to check.
+const ttk_affine_term *rs_terms(int nterms, const ttk_sum_term *terms, ttk_affine_term *t) {
+  for (int j = 0; terms && j < nterms && j < RS_TERMS; ++j)
+    t[j] = {-1, terms[j].transpose, terms[j].coef, terms[j].cores, terms[j].ranks, nullptr, nullptr, nullptr};
+  return terms ? t : nullptr;
+}
+
+// `ttk_prod_round_one`'s factors as the operand's one product term, weight exactly 1.0 (the bits are copied) and
+// not transposed, in *t, and the product's middle extents in inner (TT_MAXD entries): rp_check's status.
+int rp_term(int kind, int d, const double *const *a, const int64_t *a_ranks, const double *const *b,
+            const int64_t *b_ranks, const int64_t *modes, ttk_affine_term *t, int64_t *inner) {
+  int m[3 * TT_MAXD];
+  *t = {kind, 0, 1.0, a, a_ranks, b, b_ranks, modes};
+  return rp_check(kind, d, a_ranks, b_ranks, modes, inner, m);
 }
 
 // `ttk_affine_round_many`'s plan: every job prepared (ra_prepare) into tab[j], with its scratch offset behind
@@ -700,8 +630,8 @@ int rm_plan(const char *who, int njobs, const ttk_affine_job *jobs, double *info
     char name[64];
     if (who) snprintf(name, sizeof name, "%s: job %d", who, j);
     int64_t w = 0, s = 0;
-    if (const int e = ra_prepare(who ? name : nullptr, b.d, b.inner, b.rows, b.nterms, b.terms, b.eps, b.mode,
-                                 who != nullptr, b.out, info ? info + off : nullptr, &tab[j].a, &w, &s))
+    if (const int e = ra_prepare(who ? name : nullptr, RA_RULES, b.d, b.inner, b.rows, b.nterms, b.terms, b.eps,
+                                 b.mode, who != nullptr, true, b.out, info ? info + off : nullptr, &tab[j].a, &w, &s))
       return e;
     tab[j].scr = scr;
     scr += tt_even(w > 0 ? w : 2);
@@ -796,113 +726,49 @@ int ttk_round_one(ttk_ctx ctx, int d, const double *const *cores, const int64_t 
 
 int64_t ttk_sum_round_one_lds(int d, const int64_t *inner, int nterms, const ttk_sum_term *terms, int64_t *sum_ranks,
                               int64_t *bound) {
-  RtSumArg a;
-  int64_t words, sum[TT_MAXD + 1];
-  const int64_t b = rs_plan(d, inner, nterms, terms, &a, &words, sum);
-  if (b < 0) return -1;
-  for (int k = 0; sum_ranks && k <= d; ++k) sum_ranks[k] = sum[k];
-  for (int k = 0; bound && k <= d; ++k) bound[k] = a.p.q[k];
-  return b;
+  ttk_affine_term t[RS_TERMS];
+  return ra_lds(d, inner, nterms, rs_terms(nterms, terms, t), true, sum_ranks, bound);
 }
 
 int ttk_sum_round_one(ttk_ctx ctx, int d, const int64_t *inner, const int64_t *rows, int nterms,
                       const ttk_sum_term *terms, double eps, int mode, double *const *out, double *info) {
   ttk::CtxScope scope(ctx);
-  RtSumArg a;
-  int64_t words = 0, sum[TT_MAXD + 1];
-  const bool ok = out && info && eps >= 0.0 && eps <= 1.79769313486231570e308 && (mode == 0 || mode == 1);
-  const int64_t shm = ok ? rs_plan(d, inner, nterms, terms, &a, &words, sum) : -2;
-  if (const int e = tt_plan_status(
-          shm,
-          "ttk_sum_round_one: bad arguments (d >= 2, 1 to 4 terms, every rank and extent >= 1, boundary ranks 1, no "
-          "null pointer, coef finite, transpose 0 or 1, eps finite and >= 0, mode 0 or 1)",
-          "ttk_sum_round_one: the sum does not fit one workgroup's LDS (ttk_sum_round_one_lds)"))
+  RtAffineArg a;
+  ttk_affine_term t[RS_TERMS];
+  int64_t words = 0, shm = 0;
+  if (const int e = ra_prepare("ttk_sum_round_one", RS_RULES, d, inner, rows, nterms, rs_terms(nterms, terms, t), eps,
+                               mode, true, false, out, info, &a, &words, &shm))
     return e;
-  bool transposed = false;
-  for (int j = 0; j < nterms; ++j) transposed |= terms[j].transpose != 0;
-  if (transposed && !rows) {
-    ttk::set_error("ttk_sum_round_one: a transposed term needs rows");
-    return TTK_ERR_ARG;
-  }
-  for (int k = 0; k < d; ++k) {
-    if (rows && (rows[k] < 1 || inner[k] % rows[k] != 0)) {
-      ttk::set_error("ttk_sum_round_one: rows[%d] does not divide inner[%d]", k, k);
-      return TTK_ERR_ARG;
-    }
-    if (!out[k]) {
-      ttk::set_error("ttk_sum_round_one: null out %d", k);
-      return TTK_ERR_ARG;
-    }
-    if (rows) a.n1[k] = (int)rows[k];
-    a.p.out[k] = out[k];
-  }
-  const double e = (mode ? eps / 2.0 : eps) / std::sqrt((double)(d - 1));
-  a.p.thr2 = e * e;
-  a.p.track = mode;
-  a.p.info = info;
-  TtScratch w(ttk::ctx().stream);  // the orthogonalised cores 1 .. d-1
-  TTK_HIP(w.alloc(words));
-  tt_lds_attr(retract_kernel<true, RtSumArg>, shm);
-  hipLaunchKernelGGL((retract_kernel<true, RtSumArg>), dim3(1), dim3(a.p.nt), (size_t)shm, w.st, a, w.get());
-  TTK_LAUNCH_CHECK();
-  return TTK_OK;
+  return ra_launch(a, words, shm);
 }
 
 int64_t ttk_prod_round_one_lds(int kind, int d, const int64_t *a_ranks, const int64_t *b_ranks, const int64_t *modes,
                                int64_t *prod_ranks, int64_t *bound) {
-  RtProdArg a;
-  int64_t words, prod[TT_MAXD + 1];
-  const int64_t b = rp_plan(kind, d, a_ranks, b_ranks, modes, &a, &words, prod);
-  if (b < 0) return -1;
-  for (int k = 0; prod_ranks && k <= d; ++k) prod_ranks[k] = prod[k];
-  for (int k = 0; bound && k <= d; ++k) bound[k] = a.p.q[k];
-  return b;
+  ttk_affine_term t;
+  int64_t inner[TT_MAXD];
+  if (rp_term(kind, d, nullptr, a_ranks, nullptr, b_ranks, modes, &t, inner)) return -1;
+  return ra_lds(d, inner, 1, &t, false, prod_ranks, bound);
 }
 
 int ttk_prod_round_one(ttk_ctx ctx, int kind, int d, const double *const *a, const int64_t *a_ranks,
                        const double *const *b, const int64_t *b_ranks, const int64_t *modes, double eps, int mode,
                        double *const *out, double *info) {
   ttk::CtxScope scope(ctx);
-  RtProdArg g;
-  int64_t words = 0, prod[TT_MAXD + 1];
-  const bool ok = a && b && out && info && eps >= 0.0 && eps <= 1.79769313486231570e308 && (mode == 0 || mode == 1);
-  const int64_t shm = ok ? rp_plan(kind, d, a_ranks, b_ranks, modes, &g, &words, prod) : -2;
-  if (const int e = tt_plan_status(
-          shm,
-          "ttk_prod_round_one: bad arguments (kind 0 to 3, d >= 2, every rank and extent >= 1, boundary ranks 1, no "
-          "null pointer, eps finite and >= 0, mode 0 or 1)",
-          "ttk_prod_round_one: the product does not fit one workgroup's LDS (ttk_prod_round_one_lds)"))
+  const char *who = "ttk_prod_round_one";
+  RtAffineArg g;
+  ttk_affine_term t;
+  int64_t words = 0, shm = 0, inner[TT_MAXD];
+  if (const int chk = (a && b) ? rp_term(kind, d, a, a_ranks, b, b_ranks, modes, &t, inner) : -2)
+    return ra_fail(who, RP_RULES, chk);
+  if (const int e = ra_prepare(who, RP_RULES, d, inner, nullptr, 1, &t, eps, mode, true, false, out, info, &g, &words,
+                               &shm))
     return e;
-  for (int k = 0; k < d; ++k) {
-    if (!a[k] || !b[k] || !out[k]) {
-      ttk::set_error("ttk_prod_round_one: null core %d", k);
-      return TTK_ERR_ARG;
-    }
-    g.a[k] = a[k];
-    g.b[k] = b[k];
-    g.p.out[k] = out[k];
-  }
-  const double e = (mode ? eps / 2.0 : eps) / std::sqrt((double)(d - 1));
-  g.p.thr2 = e * e;
-  g.p.track = mode;
-  g.p.info = info;
-  TtScratch w(ttk::ctx().stream);  // the orthogonalised cores 1 .. d-1
-  TTK_HIP(w.alloc(words));
-  tt_lds_attr(retract_kernel<true, RtProdArg>, shm);
-  hipLaunchKernelGGL((retract_kernel<true, RtProdArg>), dim3(1), dim3(g.p.nt), (size_t)shm, w.st, g, w.get());
-  TTK_LAUNCH_CHECK();
-  return TTK_OK;
+  return ra_launch(g, words, shm);
 }
 
 int64_t ttk_affine_round_one_lds(int d, const int64_t *inner, int nterms, const ttk_affine_term *terms,
                                  int64_t *sum_ranks, int64_t *bound) {
-  RtAffineArg a;
-  int64_t words, sum[TT_MAXD + 1];
-  const int64_t b = ra_plan(d, inner, nterms, terms, &a, &words, sum);
-  if (b < 0) return -1;
-  for (int k = 0; sum_ranks && k <= d; ++k) sum_ranks[k] = sum[k];
-  for (int k = 0; bound && k <= d; ++k) bound[k] = a.p.q[k];
-  return b;
+  return ra_lds(d, inner, nterms, terms, true, sum_ranks, bound);
 }
 
 int ttk_affine_round_one(ttk_ctx ctx, int d, const int64_t *inner, const int64_t *rows, int nterms,
@@ -910,15 +776,10 @@ int ttk_affine_round_one(ttk_ctx ctx, int d, const int64_t *inner, const int64_t
   ttk::CtxScope scope(ctx);
   RtAffineArg a;
   int64_t words = 0, shm = 0;
-  if (const int e = ra_prepare("ttk_affine_round_one", d, inner, rows, nterms, terms, eps, mode, true, out, info, &a,
-                               &words, &shm))
+  if (const int e = ra_prepare("ttk_affine_round_one", RA_RULES, d, inner, rows, nterms, terms, eps, mode, true, true,
+                               out, info, &a, &words, &shm))
     return e;
-  TtScratch w(ttk::ctx().stream);  // the orthogonalised cores 1 .. d-1
-  TTK_HIP(w.alloc(words));
-  tt_lds_attr(retract_kernel<true, RtAffineArg>, shm);
-  hipLaunchKernelGGL((retract_kernel<true, RtAffineArg>), dim3(1), dim3(a.p.nt), (size_t)shm, w.st, a, w.get());
-  TTK_LAUNCH_CHECK();
-  return TTK_OK;
+  return ra_launch(a, words, shm);
 }
 
 int64_t ttk_affine_round_many_lds(int njobs, const ttk_affine_job *jobs, int64_t *info_off, int *threads) {

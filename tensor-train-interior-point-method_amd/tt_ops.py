@@ -333,7 +333,7 @@ def _native_round(tt, eps, mode):
     mids = [tuple(c.shape[1:-1]) for c in tt]
     ptrs = (ctypes.c_void_p * d)(*[c.data_ptr() for c in cs])
     inner = (ctypes.c_int64 * d)(*[int(np.prod(m)) for m in mids])
-    ranks = (ctypes.c_int64 * (d + 1))(*([tt[0].shape[0]] + [c.shape[-1] for c in tt]))
+    ranks = _rank_array(tt)
     tail = ctypes.c_double(0.0)
     D._stream()
     D.check(D.lib.ttk_round(D.ctx(), d, ptrs, inner, ranks, float(eps), mode, ctypes.byref(tail)), "round")
@@ -375,17 +375,15 @@ def _round_one(tt, eps, mode, plan=None):
     d = len(tt)
     inner, ranks, bound = plan or _round_one_plan(tt)
     assert list(bound) == retraction_ranks(inner, ranks, [1 << 62] * (d - 1)), list(bound)
-    outs, _ = _packed_out(tt, list(bound), inner)
+    outs = _packed_flat(list(bound), inner)
     keep = [D.contig(c) for c in tt]  # the contiguous inputs stay alive until the call is enqueued
     P = ctypes.c_void_p * d
     info = D.empty(d + 2)
     D._stream()
     D.check(D.lib.ttk_round_one(D.ctx(), d, P(*[c.data_ptr() for c in keep]), inner, ranks, float(eps), mode,
                                 P(*[o.data_ptr() for o in outs]), info.data_ptr()), "round_one")
-    got = D.read(info)
-    q = [int(v) for v in got[:d + 1]]
-    tt[:] = [o[:q[k] * inner[k] * q[k + 1]].view(q[k], *tt[k].shape[1:-1], q[k + 1]) for k, o in enumerate(outs)]
-    return tt, (pow(float(got[d + 1]), 1.0 / (2 * d)) if mode else None)
+    tt[:], factor = _round_one_finish(outs, D.read(info), inner, [c.shape[1:-1] for c in tt], mode, d)
+    return tt, factor
 
 
 def tt_rank_reduce(tt, eps=1e-18):
@@ -504,7 +502,7 @@ def _sum_round_one_plan(trains, coeffs, transposed):
     rows = (I64 * d)(*[int(m[0]) for m in mids]) if any(transposed) else None
     keep = [[D.contig(c) for c in t] for t in trains]  # the contiguous inputs stay alive until the call is enqueued
     ptrs = [P(*[c.data_ptr() for c in t]) for t in keep]
-    ranks = [(I64 * (d + 1))(*([t[0].shape[0]] + [c.shape[-1] for c in t])) for t in trains]
+    ranks = [_rank_array(t) for t in trains]
     terms = (SumTerm * n)(*[SumTerm(ctypes.cast(p, vp), ctypes.cast(r, vp), c, int(tr))
                             for p, r, c, tr in zip(ptrs, ranks, coeffs, transposed)])
     sums, bound = (I64 * (d + 1))(), (I64 * (d + 1))()
@@ -530,16 +528,13 @@ def _sum_round_one(plan, eps, mode):
     (tt, tail factor or None); the caller's tensors are never written."""
     (d, inner, rows, n, terms), sums, bound, mids, keep = plan
     assert bound == retraction_ranks(inner, sums, [1 << 62] * (d - 1)), bound
-    outs, _ = _packed_out(keep[0][0], bound, inner)
+    outs = _packed_flat(bound, inner)
     P = ctypes.c_void_p * d
     info = D.empty(d + 2)
     D._stream()
     D.check(D.lib.ttk_sum_round_one(D.ctx(), d, inner, rows, n, terms, float(eps), mode,
                                     P(*[o.data_ptr() for o in outs]), info.data_ptr()), "sum_round_one")
-    got = D.read(info)
-    q = [int(v) for v in got[:d + 1]]
-    tt = [o[:q[k] * inner[k] * q[k + 1]].view(q[k], *mids[k], q[k + 1]) for k, o in enumerate(outs)]
-    return tt, (pow(float(got[d + 1]), 1.0 / (2 * d)) if mode else None)
+    return _round_one_finish(outs, D.read(info), inner, mids, mode, d)
 
 
 def _sum_native(trains, coeffs, transposed, eps, mode):
@@ -603,22 +598,40 @@ def _inner(c):
     return int(np.prod(c.shape[1:-1])) if c.dim() > 2 else 1
 
 
+def _rank_array(t):
+    """ctypes int64 bond ranks of a train: d + 1 entries, boundaries included"""
+    return (ctypes.c_int64 * (len(t) + 1))(*([t[0].shape[0]] + [c.shape[-1] for c in t]))
+
+
 def _tt_extents(*trains):
     """ctypes int64 arrays for the native rounding calls: the middle extents of the first train (d entries),
-    then one bond-rank array per train (d + 1 entries, boundaries included)."""
-    d = len(trains[0])
-    I64 = ctypes.c_int64
-    inner = (I64 * d)(*[_inner(c) for c in trains[0]])
-    return (inner,) + tuple((I64 * (d + 1))(*([t[0].shape[0]] + [c.shape[-1] for c in t])) for t in trains)
+    then one bond-rank array per train (`_rank_array`)."""
+    inner = (ctypes.c_int64 * len(trains[0]))(*[_inner(c) for c in trains[0]])
+    return (inner,) + tuple(_rank_array(t) for t in trains)
+
+
+def _packed(sizes):
+    """One fresh buffer cut into flat slices of these sizes, every one at a 16-byte aligned offset."""
+    offs = np.concatenate(([0], np.cumsum([(s + 1) & ~1 for s in sizes])))
+    buf = D.empty(int(offs[-1]))
+    return [buf[int(o):int(o) + s] for o, s in zip(offs, sizes)]
 
 
 def _packed_flat(rk, inner):
     """One fresh buffer for the output cores of ranks `rk` and middle extents `inner`: its flat slices, one per
     core (what a native call writes)."""
-    sizes = [rk[k] * inner[k] * rk[k + 1] for k in range(len(inner))]
-    offs = np.concatenate(([0], np.cumsum([(s + 1) & ~1 for s in sizes])))  # 16-byte aligned cores
-    buf = D.empty(int(offs[-1]))
-    return [buf[int(o):int(o) + s] for o, s in zip(offs, sizes)]
+    return _packed([rk[k] * inner[k] * rk[k + 1] for k in range(len(inner))])
+
+
+def _round_one_finish(outs, got, inner, mids, mode, d):
+    """What a one-launch rounding left behind, as the caller's result.  outs: the flat buffers it wrote, sized by
+    the bound ranks; got: its info words as read -- the d + 1 decided ranks, the discarded tail and, where the entry
+    has it (d + 3 words), the squared norm; mids: the middle shape of every core.  Returns (tt, tail factor or None)
+    with the cores views of the written fronts, and the squared norm as a third entry where `got` holds one."""
+    q = [int(v) for v in got[:d + 1]]
+    tt = [o[:q[k] * inner[k] * q[k + 1]].view(q[k], *mids[k], q[k + 1]) for k, o in enumerate(outs)]
+    res = tt, (pow(float(got[d + 1]), 1.0 / (2 * d)) if mode else None)
+    return res + (float(got[d + 2]),) if len(got) > d + 2 else res
 
 
 def _packed_out(tt, rk, inner):
@@ -1028,8 +1041,7 @@ def _native_zipup(kind, a, b, eps, out_modes):
     rounding; the same einsum plans and rounding launches as the Python composition below, so
     bit-identical to it).  out_modes[k]: the product core's physical shape."""
     d = len(a)
-    ar = [a[0].shape[0]] + [c.shape[-1] for c in a]
-    br = [b[0].shape[0]] + [c.shape[-1] for c in b]
+    ar, br = _rank_array(a), _rank_array(b)
     mids = _zipup_modes(kind, a, b)
     inner = [int(np.prod(m)) for m in out_modes]
     outs = [D.empty(ar[k] * br[k] * inner[k] * ar[k + 1] * br[k + 1]) for k in range(d)]
@@ -1039,8 +1051,8 @@ def _native_zipup(kind, a, b, eps, out_modes):
     I64 = ctypes.c_int64
     ranks = (I64 * (d + 1))()
     D._stream()
-    D.check(D.lib.ttk_zipup(D.ctx(), kind, d, (P * d)(*[c.data_ptr() for c in ca]), (I64 * (d + 1))(*ar),
-                            (P * d)(*[c.data_ptr() for c in cb]), (I64 * (d + 1))(*br), (I64 * (3 * d))(*mids),
+    D.check(D.lib.ttk_zipup(D.ctx(), kind, d, (P * d)(*[c.data_ptr() for c in ca]), ar,
+                            (P * d)(*[c.data_ptr() for c in cb]), br, (I64 * (3 * d))(*mids),
                             float(eps), (P * d)(*[o.data_ptr() for o in outs]), ranks), "zipup")
     return [o[:ranks[k] * inner[k] * ranks[k + 1]].view(ranks[k], *out_modes[k], ranks[k + 1])
             for k, o in enumerate(outs)]
@@ -1075,8 +1087,7 @@ def _prod_round_one_plan(kind, a, b):
     if d < 2 or len(b) != d:
         return None
     I64, P = ctypes.c_int64, ctypes.c_void_p * d
-    ar = (I64 * (d + 1))(*([a[0].shape[0]] + [c.shape[-1] for c in a]))
-    br = (I64 * (d + 1))(*([b[0].shape[0]] + [c.shape[-1] for c in b]))
+    ar, br = _rank_array(a), _rank_array(b)
     modes = (I64 * (3 * d))(*_zipup_modes(kind, a, b))
     prod, bound = (I64 * (d + 1))(), (I64 * (d + 1))()
     if D.lib.ttk_prod_round_one_lds(kind, d, ar, br, modes, prod, bound) < 0:
@@ -1110,10 +1121,7 @@ def _prod_round_one(plan, out_modes, eps, mode):
     D.check(D.lib.ttk_prod_round_one(D.ctx(), kind, d, pa, ar, pb, br, modes, float(eps), mode,
                                      (ctypes.c_void_p * d)(*[o.data_ptr() for o in outs]), info.data_ptr()),
             "prod_round_one")
-    got = D.read(info)
-    q = [int(v) for v in got[:d + 1]]
-    tt = [o[:q[k] * inner[k] * q[k + 1]].view(q[k], *out_modes[k], q[k + 1]) for k, o in enumerate(outs)]
-    return tt, (pow(float(got[d + 1]), 1.0 / (2 * d)) if mode else None)
+    return _round_one_finish(outs, D.read(info), inner, out_modes, mode, d)
 
 
 def _prod_native(kind, a, b, eps):
@@ -1193,13 +1201,13 @@ def _affine_round_one_plan(terms, mids):
     keep, recs = [], []
     for coef, kind, a, b, tr in terms:
         ca = [D.contig(c) for c in a]  # the contiguous inputs stay alive until the call is enqueued
-        pa, ar = P(*[c.data_ptr() for c in ca]), (I64 * (d + 1))(*([a[0].shape[0]] + [c.shape[-1] for c in a]))
+        pa, ar = P(*[c.data_ptr() for c in ca]), _rank_array(a)
         keep += [ca, pa, ar]
         if kind < 0:
             recs.append(AffineTerm(-1, int(tr), coef, ctypes.cast(pa, vp), ctypes.cast(ar, vp), None, None, None))
             continue
         cb = [D.contig(c) for c in b]
-        pb, br = P(*[c.data_ptr() for c in cb]), (I64 * (d + 1))(*([b[0].shape[0]] + [c.shape[-1] for c in b]))
+        pb, br = P(*[c.data_ptr() for c in cb]), _rank_array(b)
         modes = (I64 * (3 * d))(*_zipup_modes(kind, a, b))
         keep += [cb, pb, br, modes]
         recs.append(AffineTerm(kind, int(tr), coef, ctypes.cast(pa, vp), ctypes.cast(ar, vp), ctypes.cast(pb, vp),
@@ -1242,10 +1250,7 @@ def _affine_native(terms, eps, mode, mids=None):
     D.check(D.lib.ttk_affine_round_one(D.ctx(), d, inner, rows, n, arr, float(eps), mode,
                                        (ctypes.c_void_p * d)(*[o.data_ptr() for o in outs]), info.data_ptr()),
             "affine_round_one")
-    got = D.read(info)
-    q = [int(v) for v in got[:d + 1]]
-    tt = [o[:q[k] * inner[k] * q[k + 1]].view(q[k], *mids[k], q[k + 1]) for k, o in enumerate(outs)]
-    return tt, (pow(float(got[d + 1]), 1.0 / (2 * d)) if mode else None), float(got[d + 2])
+    return _round_one_finish(outs, D.read(info), inner, mids, mode, d)
 
 
 def tt_affine_rank_reduce(terms, eps=1e-18, with_norm2=False, mids=None):
@@ -1322,9 +1327,7 @@ def _affine_many_native(jobs):
         assert bound == retraction_ranks(inner, sums, [1 << 62] * (d - 1)), bound
         sizes += [bound[k] * inner[k] * bound[k + 1] for k in range(d)]
         at.append(len(sizes))
-    offs = np.concatenate(([0], np.cumsum([(s + 1) & ~1 for s in sizes])))  # 16-byte aligned cores
-    buf = D.empty(int(offs[-1]))
-    flat = [buf[int(o):int(o) + s] for o, s in zip(offs, sizes)]
+    flat = _packed(sizes)
     ioff = (ctypes.c_int64 * (nj + 1))()
     keep = []
     for j in range(nj):
@@ -1341,11 +1344,7 @@ def _affine_many_native(jobs):
     res = []
     for j, ((_, _, mode, mids), plan) in enumerate(zip(norm, plans)):
         d, inner = plan[0][0], plan[0][1]
-        g = got[int(ioff[j]):int(ioff[j]) + d + 3]
-        q = [int(v) for v in g[:d + 1]]
-        tt = [o[:q[k] * inner[k] * q[k + 1]].view(q[k], *mids[k], q[k + 1])
-              for k, o in enumerate(flat[at[j]:at[j + 1]])]
-        res.append((tt, (pow(float(g[d + 1]), 1.0 / (2 * d)) if mode else None), float(g[d + 2])))
+        res.append(_round_one_finish(flat[at[j]:at[j + 1]], got[int(ioff[j]):int(ioff[j + 1])], inner, mids, mode, d))
     return res
 
 

@@ -74,13 +74,14 @@ def test_fused_matches_composed_path(T, cid, monkeypatch):
     T.D.check_handoffs()
 
 
-def _abi_call(T, terms, mids, eps, mode):
-    """`ttk_affine_round_one` itself: (status, out buffers, info, d, inner, bound, (launches, waits), keep)"""
+def _abi_call(T, terms, mids, eps, mode, info=None):
+    """`ttk_affine_round_one` itself: (status, out buffers, info, d, inner, bound, (launches, waits), keep); info:
+    the caller's own buffer"""
     D = T.D
     nt, mids = T._affine_norm(terms, mids)
     (d, inner, rows, n, arr), sums, bound, keep = T._affine_round_one_plan(nt, mids)
     outs = T._packed_flat(bound, list(inner))
-    info = D.empty(d + 3)
+    info = D.empty(d + 3) if info is None else info
     P = ctypes.c_void_p * d
     D._stream()
     D.read(info)  # the allocations are done
@@ -235,6 +236,26 @@ def test_info_holds_the_squared_norm_of_the_output(T, cid):
     print(f"info[d+2] case {cid}: relative error of the norm {err:.3g}")
     assert err <= AC.RTOL, (cid, err)
     assert np.array_equal(got.view(np.int64), again.view(np.int64))
+    T.D.check_handoffs()
+
+
+@pytest.mark.parametrize("mode", (0, 1))
+def test_info_is_d_plus_3_words_and_the_last_is_overwritten(T, mode):
+    """the opposite of the sum's and the product's d + 2: a preset info[d + 2] is replaced by the squared norm of the
+    output, to the tolerance of the test above (case r, d = 3: a product and a plain term)"""
+    _, dev = _up(T, "r")
+    d = 3
+    preset = np.full(d + 3, -1.0)
+    preset[d + 2:].view(np.int64)[0] = 0x4242424242424242  # a finite double, about 1.6e11
+    rc, outs, info, d2, inner, _, _, _ = _abi_call(T, AC.terms("r", dev), AC.mids("r"), AC.eps("r"), mode,
+                                                   T.D.from_numpy(preset))
+    assert rc == 0 and d2 == d
+    got = T.D.read(info)
+    q = [int(v) for v in got[:d + 1]]
+    cores = [T.D.read(o[:q[k] * inner[k] * q[k + 1]]).reshape(q[k], inner[k], q[k + 1]) for k, o in enumerate(outs)]
+    want = float(np.linalg.norm(AC.dense(cores)))
+    assert int(got.view(np.int64)[d + 2]) != 0x4242424242424242 and not np.any(got == -1.0)
+    assert abs(float(np.sqrt(got[d + 2])) - want) <= AC.RTOL * want
     T.D.check_handoffs()
 
 

@@ -69,14 +69,15 @@ def test_fused_matches_composed_path(T, cid, monkeypatch):
     T.D.check_handoffs()
 
 
-def _abi_call(T, kind, a, b, eps, mode):
-    """`ttk_prod_round_one` itself: (status, out buffers, info, d, inner, bound, (launches, waits), keep)"""
+def _abi_call(T, kind, a, b, eps, mode, info=None):
+    """`ttk_prod_round_one` itself: (status, out buffers, info, d, inner, bound, (launches, waits), keep); info: the
+    caller's own buffer"""
     D = T.D
     plan = T._prod_round_one_plan(kind, a, b)
     (kind, d, pa, ar, pb, br, modes), prod, bound, keep = plan
     inner = [int(np.prod(m)) for m in T._prod_out_modes(kind, a, b)]
     outs = T._packed_flat(bound, inner)
-    info = D.empty(d + 2)
+    info = D.empty(d + 2) if info is None else info
     P = ctypes.c_void_p * d
     D._stream()
     D.read(info)  # the allocations are done
@@ -100,6 +101,29 @@ def test_abi_call_is_one_launch_and_no_wait(T, cid):
         assert got[d + 1] == 0.0
     else:
         assert abs(got[d + 1] ** (1.0 / (2 * d)) - PC.factor(cid)) <= 1e-11 * PC.factor(cid)
+    T.D.check_handoffs()
+
+
+SENTINEL = 0x4242424242424242  # a finite double (about 1.6e11) that no case's figures come near
+
+
+@pytest.mark.parametrize("mode", (0, 1))
+def test_info_is_d_plus_2_words_and_the_word_after_them_is_not_written(T, mode):
+    """`info` is d + 2 doubles: given d + 3 with the last preset, the call leaves that word's bits as they are and
+    writes info[0 .. d+1] with the bits it writes into a d + 2 buffer (case v, d = 3: matrix x vector)"""
+    _, (a, b) = _up(T, "v")
+    rc, _, info, d, _, _, _, _ = _abi_call(T, PC.kind("v"), a, b, PC.eps("v"), mode)
+    assert rc == 0 and d == 3
+    want = T.D.read(info)
+    preset = np.full(d + 3, -1.0)
+    preset[d + 2:].view(np.int64)[0] = SENTINEL
+    rc, _, wide, _, _, _, _, _ = _abi_call(T, PC.kind("v"), a, b, PC.eps("v"), mode, T.D.from_numpy(preset))
+    assert rc == 0
+    got = T.D.read(wide)
+    assert want.shape == (d + 2,) and got.shape == (d + 3,)
+    assert int(got.view(np.int64)[d + 2]) == SENTINEL
+    assert np.array_equal(got[:d + 2].view(np.int64), want.view(np.int64))
+    assert not np.any(got[:d + 2] == -1.0)  # every word before it was written: ranks >= 1, a tail >= 0
     T.D.check_handoffs()
 
 

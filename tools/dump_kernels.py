@@ -1,7 +1,7 @@
 """Dump the outputs of a fixed set of kernel calls (extreme eigenpairs, offset-table GEMMs) on seeded
 inputs, so two library builds can be compared bit for bit (tools/cmp_dump.py).  A second argument
 keeps only the arrays whose name starts with it and skips the sections that have none:
-`python tools/dump_kernels.py out.npz round_` dumps the three native TT roundings alone.
+`python tools/dump_kernels.py out.npz round_` dumps the native TT roundings alone.
 
     TTK_LIB_PATH=old.so python tools/dump_kernels.py gpurun_out/a.npz
     python tools/dump_kernels.py gpurun_out/b.npz        # then compare the two files on the host"""
@@ -17,8 +17,9 @@ from ttipm_amd._lib import lib  # noqa: E402
 
 
 def rounding(out):
-    """The output cores of `ttk_rand_orth`, `ttk_nystroem`, `ttk_retract` and `ttk_round_one`: every fixture case that
-    takes the native path, the two seeded inputs of the device tests and the all-zero train."""
+    """The output cores of `ttk_rand_orth`, `ttk_nystroem`, `ttk_retract`, `ttk_round_one`, `ttk_sum_round_one` and
+    `ttk_prod_round_one`: every fixture case that takes the native path, the two seeded inputs of the device tests
+    and the all-zero train."""
     from tests import nystroem_cases as NC, randorth_cases as RO, retract_cases as RT
     from ttipm_amd import tt_ops as T
 
@@ -52,6 +53,20 @@ def rounding(out):
             dump(f"round_one_{cid}", 2, lambda tt: T.tt_rank_reduce(tt, R1.eps(cid)), R1.train(cid))
     finally:
         T.ROUND_ONE = old
+    from tests import prod_round_cases as PC, sum_round_cases as SC
+    old, T.SUM_ROUND_ONE, T.PROD_ROUND_ONE = (T.SUM_ROUND_ONE, T.PROD_ROUND_ONE), True, True
+    try:
+        for cid in SC.FIT:  # `ttk_sum_round_one` / `ttk_prod_round_one` and the copy kernel of the one read
+            if SC.mode(cid) == 0:
+                dump(f"round_sum_{cid}", 2, lambda *ts: SC.public(T, cid, list(ts)), *SC.stored(cid))
+        for cid in PC.FIT:
+            a, b = PC.factors(cid)
+            if b is a:
+                dump(f"round_prod_{cid}", 2, lambda x: PC.public(T, cid, x, x), a)
+            else:
+                dump(f"round_prod_{cid}", 2, lambda x, y: PC.public(T, cid, x, y), a, b)
+    finally:
+        T.SUM_ROUND_ONE, T.PROD_ROUND_ONE = old
 
 
 def kernels(out):
