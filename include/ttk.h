@@ -806,6 +806,43 @@ int64_t ttk_split_kick_lds(int rev, int a, int b, int p, int r, int r_add, int64
 int ttk_split_kick(ttk_ctx ctx, int rev, int a, int b, int p, int r, int r_add, const double *U, const double *S,
                    const double *Vt, const double *G, double *s1, double *s2);
 
+/* The whole tail of a two-site local solve of the step-size eigen-ALS in one launch (`_step_size_local_solve`,
+ * src/tt_als.py:1022-1037): normalise, truncation SVD, `prune_singular_vals`' rank rule (cy_src/tt_ops_cy.pyx:
+ * 161-177) capped by max_rank, `_add_kick_rank` / `_add_kick_rank_rev` (:1041-1053) and the product with
+ * diag(S) Vt -- ttk_split_kick with the SVD in front of it and the rank decided on the device.  One workgroup,
+ * bounded loops and workgroup barriers only; it waits for no other workgroup and reads nothing back; the call
+ * returns after enqueueing one launch on the context's stream.
+ * M: the two-site solution as it lies, a x b row-major, the same for both directions; rev = 1 factors M^T by
+ * indexing.  G: the Gaussian block, a x r_add (rev 0) or r_add x b (rev 1).  unit != 0 scales M by 1 / ||M||_F
+ * first (a fixed tree sum; a zero norm scales by 1, so the zero matrix gives a finite zero product and r = 1).
+ * With p = min(a, b): one-sided Jacobi SVD of whichever of M and M^T has fewer rows, then
+ * r = min(prune(S, trunc_tol), max_rank) with the tail sums in np.cumsum's order as ttk_round_one forms them,
+ * then ttk_split_kick's factorisation of [U[:, :r] | G] (rev 0) or [U[:, :r]^T ; G] (rev 1) in LAPACK's
+ * dgeqrf / dgerqf gauge, q = min(rev ? b : a, r + r_add).  The outputs do not depend on the signs of the
+ * singular vectors.
+ * s1 (a x q) and s2 (q x b) are written contiguous, leading dimensions q and b, into buffers of capacity
+ * a qmax and qmax b, qmax = min(rev ? b : a, min(p, max_rank) + r_add) from ttk_trunc_kick_lds.
+ * info (4 + p doubles; it may point into a larger device buffer, so that the caller reads it together with other
+ * scalars): [0] r, [1] q, [2] the Jacobi sweeps taken (negative if their cap was hit), [3] ||M||_F as found,
+ * [4 .. 4 + p) S descending, of the scaled matrix.
+ * Each product element is one fma chain with k ascending and every reduction a fixed tree: two calls on the
+ * same input give the same bits.
+ * ttk_trunc_kick_lds (host only): the bytes of LDS, or -1 when the matrix, the p x p rotations, the concatenated
+ * matrix and Q do not fit one workgroup (at most 160 KiB) or the arguments are invalid -- the caller then
+ * composes the tail from ttk_svd, the host's rank rule and ttk_split_kick or its composition; fills *qmax_out
+ * unless NULL, and leaves it untouched on -1.  ttk_trunc_kick validates on the host (rev 0 or 1, a, b, r_add,
+ * max_rank >= 1, trunc_tol >= 0 and finite, no null pointer, the LDS fit) and returns TTK_ERR_ARG without
+ * launching when a check fails.
+ * ttk_trunc_kick_read: the same launch with the info block read in the same call, as ttk_svd_tol_read reads S:
+ * the kernel stores info in the context's host-coherent block, the call waits for the stream once and copies
+ * the 4 + p doubles to info_host (host memory).  One launch and one host wait, no copy launch; for a caller with
+ * nothing else to read. */
+int64_t ttk_trunc_kick_lds(int rev, int a, int b, int r_add, int max_rank, int64_t *qmax_out);
+int ttk_trunc_kick(ttk_ctx ctx, int rev, int a, int b, int r_add, int unit, double trunc_tol, int max_rank,
+                   const double *M, const double *G, double *s1, double *s2, double *info);
+int ttk_trunc_kick_read(ttk_ctx ctx, int rev, int a, int b, int r_add, int unit, double trunc_tol, int max_rank,
+                        const double *M, const double *G, double *s1, double *s2, double *info_host);
+
 /* Dense Schur-complement local KKT solve in one call (SURVEY §8(b) `ttk_local_assemble` +
  * `ttk_dense_schur_solve`; the dense branch of `_ipm_local_solver`, src/tt_ipm.py:183-229):
  * assembles L_XI = B22 diag(inv_I), L_eq = B01, L_Z = B21 (each 'lsr,smnS,LSR->lmLrnR'), Cholesky of

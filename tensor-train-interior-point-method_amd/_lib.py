@@ -101,6 +101,9 @@ _SIGS = {
     "ttk_affine_round_many": (i32, [vp, i32, vp, vp]),
     "ttk_split_kick_lds": (i64, [i32, i32, i32, i32, i32, i32, vp]),
     "ttk_split_kick": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "ttk_trunc_kick_lds": (i64, [i32, i32, i32, i32, i32, vp]),
+    "ttk_trunc_kick": (i32, [vp, i32, i32, i32, i32, i32, f64, i32, vp, vp, vp, vp, vp]),
+    "ttk_trunc_kick_read": (i32, [vp, i32, i32, i32, i32, i32, f64, i32, vp, vp, vp, vp, vp]),
     "ttk_dense_schur_solve": (i32, [vp, i64, i64, i64, vp, vp, vp, vp, vp]),
     "ttk_dense_schur_solve_ineq": (i32, [vp, i64, i64, i64, vp, vp, vp, vp]),
     "ttk_fused_set_mfma": (i32, [i32]),

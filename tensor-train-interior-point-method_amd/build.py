@@ -10,7 +10,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libttk.so")
 SOURCES = ["ttk_runtime.hip", "ttk_contract.hip", "ttk_einsum.hip", "ttk_linalg.hip", "ttk_lgmres.hip", "ttk_dense.hip",
-           "ttk_host.hip", "ttk_randorth.hip", "ttk_nystroem.hip", "ttk_retract.hip", "ttk_split_kick.hip"]
+           "ttk_host.hip", "ttk_randorth.hip", "ttk_nystroem.hip", "ttk_retract.hip", "ttk_split_kick.hip",
+           "ttk_trunc_kick.hip"]
 HEADERS = ["ttk_common.h", "ttk_internal.h", "ttk_tt_gemm.h", os.path.join("..", "..", "include", "ttk.h")]
 FLAGS = ["-O3", "-fPIC", "--offload-arch=gfx950", "-std=c++17", "-Wno-unused-variable",
          "-Wno-unused-but-set-variable", "-I" + os.path.join(HERE, "..", "include")]

@@ -383,9 +383,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                       const std::vector<at::Tensor> &x0, const at::Tensor &o3, int64_t nswp, double tol,
                       int64_t size_limit, double trunc_tol, int64_t max_rank, int64_t max_dense,
                       pybind11::array_t<uint32_t, pybind11::array::c_style | pybind11::array::forcecast> key,
-                      int64_t pos, int64_t has_gauss, double gauss) {  // without the trailing per-call flag
+                      int64_t pos, int64_t has_gauss, double gauss) {  // without the trailing per-call flags
     return eig::eig_als(A, Dl, x0, o3, nswp, tol, size_limit, trunc_tol, max_rank, max_dense, key, pos, has_gauss,
-                        gauss, false);
+                        gauss, false, false);
+  });
+  m.def("eig_als", [](const std::vector<at::Tensor> &A, const std::vector<at::Tensor> &Dl,
+                      const std::vector<at::Tensor> &x0, const at::Tensor &o3, int64_t nswp, double tol,
+                      int64_t size_limit, double trunc_tol, int64_t max_rank, int64_t max_dense,
+                      pybind11::array_t<uint32_t, pybind11::array::c_style | pybind11::array::forcecast> key,
+                      int64_t pos, int64_t has_gauss, double gauss, bool split_kick) {  // split_kick's flag alone
+    return eig::eig_als(A, Dl, x0, o3, nswp, tol, size_limit, trunc_tol, max_rank, max_dense, key, pos, has_gauss,
+                        gauss, split_kick, false);
   });
   m.def("legacy_randn", &eig::legacy_randn);
   m.def("prune_singular_vals", &eig::prune_singular_vals);

@@ -36,6 +36,9 @@ using batch_fn = int (*)(void *);
 using split_kick_lds_fn = int64_t (*)(int, int, int, int, int, int, int64_t *);
 using split_kick_fn = int (*)(void *, int, int, int, int, int, int, const double *, const double *, const double *,
                               const double *, double *, double *);
+using trunc_kick_lds_fn = int64_t (*)(int, int, int, int, int, int64_t *);
+using trunc_kick_fn = int (*)(void *, int, int, int, int, int, double, int, const double *, const double *, double *,
+                              double *, double *);
 
 struct Fns {
   svd_work_fn svd_work = nullptr;
@@ -54,6 +57,9 @@ struct Fns {
   batch_fn batch_begin = nullptr, batch_end = nullptr;
   split_kick_lds_fn split_kick_lds = nullptr;  // ttk_split_kick_lds, ttk_split_kick (optional 16th, 17th address)
   split_kick_fn split_kick = nullptr;
+  // ttk_trunc_kick_lds, ttk_trunc_kick, ttk_trunc_kick_read (optional 18th to 20th address)
+  trunc_kick_lds_fn trunc_kick_lds = nullptr;
+  trunc_kick_fn trunc_kick = nullptr, trunc_kick_read = nullptr;
 } F;
 
 // ---------------------------------------------------------------- NumPy's legacy Gaussian stream
@@ -310,6 +316,7 @@ struct Solver {
   double tol = 1e-8, trunc_tol = 0.0;
   int64_t size_limit = 256, max_rank = 1, max_dense = 4096;
   bool split_kick = false;  // dev.SPLIT_KICK as this call found it
+  bool trunc_kick = false;  // dev.TRUNC_KICK as this call found it
   // _Deferred: (ev, ||r||^2) per dense local solve of a half-sweep, read once after it
   at::Tensor dbuf;
   int dn = 0;
@@ -377,11 +384,18 @@ struct Solver {
     dn = 0;
   }
 
-  // the caller's truncation SVD, enqueued behind the eigensolve (tt_eig._dense_step's `post`)
+  // dev.trunc_kick's result: the two output buffers and the info block on the device
+  struct TK {
+    at::Tensor s1, s2, info;
+  };
+  // the caller's truncation SVD, enqueued behind the eigensolve (tt_eig._dense_step's `post`); tk instead: the
+  // caller's whole tail (ttk_trunc_kick), which takes the eigenvector as the solver left it
   using PostFn = std::function<Ops::SVD(const at::Tensor &, const at::Tensor &)>;
+  using PostTk = std::function<TK(const at::Tensor &, const at::Tensor &)>;
   struct Post {
     int64_t k;
     PostFn fn;
+    PostTk tk;
   };
   struct StepOut {
     at::Tensor sol;
@@ -389,6 +403,9 @@ struct Solver {
     Res res;
     bool has_pre = false;
     Ops::SVD pre;
+    bool has_tk = false;
+    TK tk;
+    std::vector<double> tkinfo;  // the info block as read with the eigenvalue
   };
 
   // tt_eig._dense_step (src/tt_als.py:957-996,1060-1101)
@@ -401,14 +418,25 @@ struct Solver {
     if (post) {
       at::Tensor comb = o.emp({1 + post->k});
       sol = o.syev_extreme(M, false, comb.slice(0, 0, 1)).second;
-      if (two_site) sol = normalized(sol);
-      Ops::SVD p = post->fn(sol, comb.slice(0, 1, 1 + post->k));
-      std::vector<double> h = o.read(comb);
-      ev = h[0];
-      if (!(ev < 0)) {
-        p.s.assign(h.begin() + 1, h.end());
-        out.pre = std::move(p);
-        out.has_pre = true;
+      if (post->tk) {
+        TK t = post->tk(sol, comb.slice(0, 1, 1 + post->k));
+        std::vector<double> h = o.read(comb);
+        ev = h[0];
+        if (!(ev < 0)) {
+          out.tkinfo.assign(h.begin() + 1, h.end());
+          out.tk = std::move(t);
+          out.has_tk = true;
+        }
+      } else {
+        if (two_site) sol = normalized(sol);
+        Ops::SVD p = post->fn(sol, comb.slice(0, 1, 1 + post->k));
+        std::vector<double> h = o.read(comb);
+        ev = h[0];
+        if (!(ev < 0)) {
+          p.s.assign(h.begin() + 1, h.end());
+          out.pre = std::move(p);
+          out.has_pre = true;
+        }
       }
     } else {
       auto r = o.syev_extreme(M, false, c10::nullopt);
@@ -511,6 +539,45 @@ struct Solver {
     return {o.contig(k.a).view({sh[0], sh[1], k.r}), o.contig(k.b).view({k.r, sh[2], sh[3]})};
   }
 
+  // tt_eig._trunc_kick_fits: the output bound of ttk_trunc_kick where this split takes it, else -1
+  int64_t tk_qmax(const std::array<int64_t, 4> &sh, bool bwd) {
+    if (!trunc_kick || !F.trunc_kick || !F.trunc_kick_read || !F.trunc_kick_lds) return -1;
+    int64_t q = 0;
+    if (F.trunc_kick_lds(bwd ? 1 : 0, (int)(sh[0] * sh[1]), (int)(sh[2] * sh[3]), 4, (int)max_rank, &q) < 0) return -1;
+    return q;
+  }
+  // dev.trunc_kick: one launch, no read; info into info_out when given
+  TK tk_call(const at::Tensor &M, const std::array<int64_t, 4> &sh, bool bwd, int unit, const at::Tensor &G,
+             int64_t qmax, c10::optional<at::Tensor> info_out) {
+    const int64_t a = sh[0] * sh[1], b = sh[2] * sh[3];
+    TK t{o.emp({a * qmax}), o.emp({qmax * b}), info_out.has_value() ? *info_out : o.emp({4 + std::min(a, b)})};
+    // a null context: the one dev._stream() bound to this thread
+    o.ok(F.trunc_kick(nullptr, bwd ? 1 : 0, (int)a, (int)b, 4, unit, trunc_tol, (int)max_rank, M.data_ptr<double>(),
+                      G.data_ptr<double>(), t.s1.data_ptr<double>(), t.s2.data_ptr<double>(),
+                      t.info.data_ptr<double>()),
+         "trunc_kick");
+    return t;
+  }
+  // dev.trunc_kick_views on the info block as read back
+  std::pair<at::Tensor, at::Tensor> tk_views(const TK &t, const std::vector<double> &info,
+                                             const std::array<int64_t, 4> &sh) {
+    const int64_t a = sh[0] * sh[1], b = sh[2] * sh[3], q = (int64_t)info[1];
+    return {t.s1.slice(0, 0, a * q).view({sh[0], sh[1], q}), t.s2.slice(0, 0, q * b).view({q, sh[2], sh[3]})};
+  }
+  // tt_eig._trunc_split: ttk_trunc_kick_read, the call with its info read in it
+  std::pair<at::Tensor, at::Tensor> tk_split(const at::Tensor &sol, const std::array<int64_t, 4> &sh, bool bwd,
+                                             int unit, const at::Tensor &G, int64_t qmax) {
+    const int64_t a = sh[0] * sh[1], b = sh[2] * sh[3];
+    at::Tensor M = o.contig(sol);
+    TK t{o.emp({a * qmax}), o.emp({qmax * b}), at::Tensor()};
+    std::vector<double> info((size_t)(4 + std::min(a, b)));
+    o.ok(F.trunc_kick_read(nullptr, bwd ? 1 : 0, (int)a, (int)b, 4, unit, trunc_tol, (int)max_rank,
+                           M.data_ptr<double>(), G.data_ptr<double>(), t.s1.data_ptr<double>(),
+                           t.s2.data_ptr<double>(), info.data()),
+         "trunc_kick");
+    return tk_views(t, info, sh);
+  }
+
   struct Local {
     at::Tensor s1, s2;
     double step;
@@ -534,8 +601,18 @@ struct Solver {
     at::Tensor Ar = o.E(TWO_SITE, {XAX_k, A_k, A_kp1, XAX_k2});
     o.end();
     at::Tensor Dm = sym(Dr, m), Am = sym(Ar, m);
+    const int64_t qmax = tk_qmax(sh, bwd);
+    if (qmax >= 0) {  // tt_eig._step_size_local_solve under dev.TRUNC_KICK: the block first, then the whole tail
+      at::Tensor G = bwd ? gauss(4, sh[2] * sh[3]) : gauss(sh[0] * sh[1], 4);
+      Post post{4 + std::min(sh[0] * sh[1], sh[2] * sh[3]), nullptr,
+                [&](const at::Tensor &v, const at::Tensor &info) { return tk_call(v, sh, bwd, 1, G, qmax, info); }};
+      StepOut so = dense_step(pv, Am, Dm, step, tol, true, &post);
+      auto s = so.has_tk ? tk_views(so.tk, so.tkinfo, sh) : tk_split(so.sol, sh, bwd, 1, G, qmax);
+      return {s.first, s.second, so.step, so.res};
+    }
     Post post{std::min(sh[0] * sh[1], sh[2] * sh[3]),
-              [&](const at::Tensor &v, const at::Tensor &S_out) { return split_svd(normalized(v), sh, bwd, S_out); }};
+              [&](const at::Tensor &v, const at::Tensor &S_out) { return split_svd(normalized(v), sh, bwd, S_out); },
+              nullptr};
     StepOut so = dense_step(pv, Am, Dm, step, tol, true, &post);
     if (so.has_pre) {
       auto s = split(at::Tensor(), sh, bwd, &so.pre);
@@ -747,7 +824,7 @@ pybind11::tuple eig_als(const std::vector<at::Tensor> &A, const std::vector<at::
                         const std::vector<at::Tensor> &x0, const at::Tensor &o3, int64_t nswp, double tol,
                         int64_t size_limit, double trunc_tol, int64_t max_rank, int64_t max_dense,
                         pybind11::array_t<uint32_t, pybind11::array::c_style | pybind11::array::forcecast> key,
-                        int64_t pos, int64_t has_gauss, double gauss, bool split_kick) {
+                        int64_t pos, int64_t has_gauss, double gauss, bool split_kick, bool trunc_kick) {
   TORCH_CHECK(F.svd_tol && F.batch_end, "ttk_host_bind: bind_eig() not called");
   TORCH_CHECK(g_einsum && g_axpby, "ttk_host_bind: bind() / bind2() not called");  // (g_stream may be the null stream)
   TORCH_CHECK(key.size() == 624, "eig_als: MT19937 key of ", key.size(), " words");
@@ -764,6 +841,7 @@ pybind11::tuple eig_als(const std::vector<at::Tensor> &A, const std::vector<at::
   s.max_rank = max_rank;
   s.max_dense = max_dense;
   s.split_kick = split_kick;
+  s.trunc_kick = trunc_kick;
   std::vector<at::Tensor> x = x0;
   int status = 0;
   std::string why;
@@ -823,7 +901,7 @@ int64_t prune_singular_vals(pybind11::array_t<double, pybind11::array::c_style |
 }
 
 void bind_eig(const std::vector<int64_t> &a) {
-  TORCH_CHECK(a.size() == 14 || a.size() == 15 || a.size() == 17, "bind_eig: ", a.size(), " addresses");
+  TORCH_CHECK(a.size() == 14 || a.size() == 15 || a.size() == 17 || a.size() == 20, "bind_eig: ", a.size(), " addresses");
   F.svd_work = reinterpret_cast<svd_work_fn>(a[0]);
   F.svd_tol = reinterpret_cast<svd_tol_fn>(a[1]);
   F.qr_work = reinterpret_cast<qr_work_fn>(a[2]);
@@ -841,6 +919,9 @@ void bind_eig(const std::vector<int64_t> &a) {
   F.svd_read = a.size() > 14 ? reinterpret_cast<svd_read_fn>(a[14]) : nullptr;  // 0 where the library lacks it
   F.split_kick_lds = a.size() > 16 ? reinterpret_cast<split_kick_lds_fn>(a[15]) : nullptr;
   F.split_kick = a.size() > 16 ? reinterpret_cast<split_kick_fn>(a[16]) : nullptr;
+  F.trunc_kick_lds = a.size() > 19 ? reinterpret_cast<trunc_kick_lds_fn>(a[17]) : nullptr;
+  F.trunc_kick = a.size() > 19 ? reinterpret_cast<trunc_kick_fn>(a[18]) : nullptr;
+  F.trunc_kick_read = a.size() > 19 ? reinterpret_cast<trunc_kick_fn>(a[19]) : nullptr;
 }
 
 }  // namespace eig

@@ -177,34 +177,6 @@ int64_t rt_plan(int d, const int64_t *inner, const int64_t *ranks, const int64_t
   return L.words * 8;
 }
 
-// The kept rank of one bond by the reference's rule (prune_singular_vals, cy_src/tt_ops_cy.pyx:161-177) on the
-// pp singular values sv[perm[0]] >= ... : sc[j] = sum_{t >= j} sv[perm[t]]^2 summed from the smallest value
-// upward (np.cumsum's order: rounded products, rounded sums), q = the first j with sc[j] < thr2 (0 if
-// none), at least 1, and pp if sc[pp-1] > thr2; the all-zero spectrum gives 1.  *tail += sc[q] when q < pp
-// and track.  The result is clamped to [1, pp] whatever the spectrum holds (a NaN compares false).
-__device__ int rt_kept_rank(const double *sv, const int *perm, int pp, double thr2, bool track, double *tail) {
-  double sc = 0.0;
-  int q = 0;
-  for (int j = pp - 1; j >= 0; --j) {
-    const double s = sv[perm[j]];
-    sc = __dadd_rn(sc, __dmul_rn(s, s));
-    if (sc < thr2) q = j;
-  }
-  q = q < 1 ? 1 : q;
-  const double last = sv[perm[pp - 1]];
-  if (__dmul_rn(last, last) > thr2) q = pp;
-  q = q > pp ? pp : q;
-  if (track && q < pp) {
-    sc = 0.0;
-    for (int j = pp - 1; j >= q; --j) {
-      const double s = sv[perm[j]];
-      sc = __dadd_rn(sc, __dmul_rn(s, s));
-    }
-    *tail += sc;
-  }
-  return q;
-}
-
 __device__ __forceinline__ const RtPlan &rt_plan_of(const RtPlan &a) { return a; }
 __device__ __forceinline__ const RtPlan &rt_plan_of(const RtAffineArg &a) { return a.p; }
 

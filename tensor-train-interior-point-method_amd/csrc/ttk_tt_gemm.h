@@ -1,6 +1,7 @@
-// What the one-workgroup TT rounding kernels (ttk_randorth.hip, ttk_nystroem.hip, ttk_retract.hip) share:
+// What the one-workgroup TT rounding kernels (ttk_randorth.hip, ttk_nystroem.hip, ttk_retract.hip) and the
+// one-workgroup splits of a local solve (ttk_split_kick.hip, ttk_trunc_kick.hip) share:
 //   device   products and loads, the right-to-left sketch step, the Householder QR, the one-sided
-//            Jacobi round and the Jacobi SVD built on it;
+//            Jacobi round and the Jacobi SVD built on it, the kept rank of a truncation;
 //   host     the planners' constants, extents check, saturating sizes and region allocator, and the
 //            entry points' scratch block, LDS attribute and plan-status mapping.
 // Each .hip file keeps its plan struct, its region sizes and its kernels' phase structure.
@@ -243,6 +244,34 @@ __device__ int *tt_jacobi_svd(double *A, double *G, double *sv, int p, int n, in
 }
 __device__ __forceinline__ int *tt_jacobi_svd(double *A, double *G, double *sv, int p, int n) {
   return tt_jacobi_svd(A, G, sv, p, n, threadIdx.x, blockDim.x);
+}
+
+// The kept rank of one truncation by the reference's rule (prune_singular_vals, cy_src/tt_ops_cy.pyx:161-177) on the
+// pp singular values sv[perm[0]] >= ... : sc[j] = sum_{t >= j} sv[perm[t]]^2 summed from the smallest value
+// upward (np.cumsum's order: rounded products, rounded sums), q = the first j with sc[j] < thr2 (0 if
+// none), at least 1, and pp if sc[pp-1] > thr2; the all-zero spectrum gives 1.  *tail += sc[q] when q < pp
+// and track.  The result is clamped to [1, pp] whatever the spectrum holds (a NaN compares false).
+__device__ int rt_kept_rank(const double *sv, const int *perm, int pp, double thr2, bool track, double *tail) {
+  double sc = 0.0;
+  int q = 0;
+  for (int j = pp - 1; j >= 0; --j) {
+    const double s = sv[perm[j]];
+    sc = __dadd_rn(sc, __dmul_rn(s, s));
+    if (sc < thr2) q = j;
+  }
+  q = q < 1 ? 1 : q;
+  const double last = sv[perm[pp - 1]];
+  if (__dmul_rn(last, last) > thr2) q = pp;
+  q = q > pp ? pp : q;
+  if (track && q < pp) {
+    sc = 0.0;
+    for (int j = pp - 1; j >= q; --j) {
+      const double s = sv[perm[j]];
+      sc = __dadd_rn(sc, __dmul_rn(s, s));
+    }
+    *tail += sc;
+  }
+  return q;
 }
 
 // ---- host: planning

@@ -747,6 +747,59 @@ def split_kick(rev, U, S, Vt, r, G):
     return s1, s2, q
 
 
+# `ttk_trunc_kick` for the tail of the eigen-ALS two-site local solves (tt_eig._step_size_local_solve, _split):
+# off by default, like TTIPM_SPLIT_KICK, over which it takes precedence where it applies.  A module attribute,
+# read at every call, so that a test can switch it.
+TRUNC_KICK = os.environ.get("TTIPM_TRUNC_KICK", "0") == "1"
+
+
+def trunc_kick_qmax(rev, a, b, r_add, max_rank):
+    """The bound qmax on the output rank of `ttk_trunc_kick` on these extents, or None where that call cannot be
+    made: the device is the CPU, the library lacks the entry point, or the working set does not fit one
+    workgroup (`ttk_trunc_kick_lds` returns -1).  Host arithmetic only: a caller asks before it draws the
+    Gaussian block."""
+    if DEV.type != "cuda" or not hasattr(lib, "ttk_trunc_kick"):
+        return None
+    q = ctypes.c_int64(0)
+    if lib.ttk_trunc_kick_lds(int(rev), int(a), int(b), int(r_add), int(max_rank), ctypes.byref(q)) < 0:
+        return None
+    return int(q.value)
+
+
+def trunc_kick(rev, M, G, trunc_tol, max_rank, unit, info_out=None, read=False):
+    """`ttk_trunc_kick`: normalise (unit), truncation SVD, the rank decision, the kicked QR / RQ and the product
+    with diag(S) Vt in one launch, no host read.  M (a, b) contiguous, the two-site solution as it lies for both
+    directions; G (a, r_add) for rev 0, (r_add, b) for rev 1.  Returns (s1buf (a * qmax,), s2buf (qmax * b,),
+    info (4 + min(a, b),)) -- `info_out`, a contiguous device slice of that length, when given -- without
+    synchronising; `trunc_kick_views` turns the read-back info into the factors.  `read`: info comes back as a
+    host array, read in the same call (`ttk_trunc_kick_read`: one launch, one host wait).  The caller has asked
+    `trunc_kick_qmax` first."""
+    assert M.is_contiguous() and G.is_contiguous()
+    a, b = M.shape
+    r_add = G.shape[0] if rev else G.shape[1]
+    qmax = trunc_kick_qmax(rev, a, b, r_add, max_rank)
+    if qmax is None:
+        raise ValueError(f"trunc_kick: ({a}, {b}) does not fit one workgroup (trunc_kick_qmax)")
+    s1, s2 = empty(a * qmax), empty(qmax * b)
+    _stream()
+    if read:
+        info = np.empty(4 + min(a, b), dtype=np.float64)
+        check(lib.ttk_trunc_kick_read(ctx(), int(rev), a, b, r_add, int(bool(unit)), float(trunc_tol), int(max_rank),
+                                      _p(M), _p(G), _p(s1), _p(s2), info.ctypes.data_as(c_dp)), "trunc_kick")
+        return s1, s2, info
+    info = empty(4 + min(a, b)) if info_out is None else info_out
+    assert info.is_contiguous() and info.numel() == 4 + min(a, b)
+    check(lib.ttk_trunc_kick(ctx(), int(rev), a, b, r_add, int(bool(unit)), float(trunc_tol), int(max_rank), _p(M),
+                             _p(G), _p(s1), _p(s2), _p(info)), "trunc_kick")
+    return s1, s2, info
+
+
+def trunc_kick_views(s1buf, s2buf, info, a, b):
+    """(s1 (a, q), s2 (q, b), r, q) from `trunc_kick`'s buffers and its info as read back (a host array)."""
+    r, q = int(info[0]), int(info[1])
+    return s1buf[:a * q].view(a, q), s2buf[:q * b].view(q, b), r, q
+
+
 def cholesky_(A):
     """In-place lower Cholesky; raises LinAlgError if not positive definite."""
     assert A.is_contiguous()

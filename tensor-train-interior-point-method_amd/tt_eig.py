@@ -119,8 +119,32 @@ def _split_svd(sol, sh, bwd, S_out=None):
     return D.svd(mat, host=S_out is None, S_out=S_out)
 
 
+def _trunc_kick_fits(sh, max_rank, bwd):
+    """whether this split takes `ttk_trunc_kick` (dev.TRUNC_KICK, and the shape fits one workgroup)"""
+    return D.TRUNC_KICK and D.trunc_kick_qmax(int(bwd), sh[0] * sh[1], sh[2] * sh[3], 4, max_rank) is not None
+
+
+def _trunc_gauss(sh, bwd):
+    """the kick block of `_kick` / `_kick_rev`: its shape does not depend on the rank, so it is drawn up front"""
+    return D.from_numpy(_rng.R().randn(4, sh[2] * sh[3]) if bwd else _rng.R().randn(sh[0] * sh[1], 4))
+
+
+def _trunc_views(s1buf, s2buf, info, sh):
+    s1, s2, _, q = D.trunc_kick_views(s1buf, s2buf, info, sh[0] * sh[1], sh[2] * sh[3])
+    return s1.view(sh[0], sh[1], q), s2.view(q, sh[2], sh[3])
+
+
+def _trunc_split(sol, sh, trunc_tol, max_rank, bwd, unit, G):
+    """the split of `sol` (normalised first with `unit`) by `ttk_trunc_kick_read`: one launch, one host wait"""
+    s1buf, s2buf, info = D.trunc_kick(int(bwd), D.contig(sol).view(sh[0] * sh[1], sh[2] * sh[3]), G, trunc_tol,
+                                      max_rank, unit, read=True)
+    return _trunc_views(s1buf, s2buf, info, sh)
+
+
 def _split(sol, sh, trunc_tol, max_rank, bwd, pre=None):
     """`pre`: the (U, S, Vt, s) of `_split_svd(sol, ...)` when already computed"""
+    if pre is None and _trunc_kick_fits(sh, max_rank, bwd):  # ttk_trunc_kick and one read of its info
+        return _trunc_split(sol, sh, trunc_tol, max_rank, bwd, 0, _trunc_gauss(sh, bwd))
     U, S, Vt, s = _split_svd(sol, sh, bwd) if pre is None else pre
     G = None
     if D.SPLIT_KICK:  # one launch (ttk_split_kick) where it fits; the draw is the composed path's, in its place
@@ -334,20 +358,22 @@ def _dense_step(prev, Am, Dm, step, eps, tag, post=None):
     speculatively right behind the eigensolve, on the branch taken when ev >= 0, and the eigenvalue
     and the k singular values come back in ONE host read; on ev < 0 that work is dropped (it has no
     side effects) and the caller redoes it on the branch's solution.  Returns (sol, step, residual,
-    pre) with pre = the SVD tuple (host singular values filled in) or None."""
+    pre) with pre = the SVD tuple (host singular values filled in) or None.
+    `post` = (k, fn, True): fn takes the eigenvector as the solver left it and normalises it itself
+    (`ttk_trunc_kick`); its tuple's last entry is likewise replaced by the k words read."""
     M = _shifted(Am, Dm, step)
     pre = None
     if post is not None:
-        k, fn = post
+        k, fn = post[:2]
         comb = D.empty(1 + k)
         _, sol = D.syev_extreme(M, largest=False, lam_out=comb[:1])
-        if tag == "two-site":
+        if tag == "two-site" and len(post) == 2:
             sol = _normalise(sol)
-        U, S, Vt, _ = fn(sol, comb[1:])
+        out = fn(sol, comb[1:])
         h = D.read(comb)
         ev = float(h[0])
         if not ev < 0:
-            pre = (U, S, Vt, h[1:])
+            pre = tuple(out[:-1]) + (h[1:],)
     else:
         ev, sol = _min_eigpair(M)
         if tag == "two-site":
@@ -420,6 +446,40 @@ def _iterative_step(prev, apply_A, apply_D, step, eps, tag):
     return sol, step, D.norm(ADp)
 
 
+def _two_site_tail(sol, sh, trunc_tol, max_rank, bwd, step, old_res):
+    """normalise and split a two-site solution that no speculative work covered (`src/tt_als.py:1022-1037`)"""
+    if _trunc_kick_fits(sh, max_rank, bwd):  # ttk_trunc_kick normalises itself
+        return _trunc_split(sol, sh, trunc_tol, max_rank, bwd, 1, _trunc_gauss(sh, bwd)) + (step, old_res)
+    sol = _normalise(sol)
+    s1, s2 = _split(sol, sh, trunc_tol, max_rank, bwd)
+    return s1, s2, step, old_res
+
+
+def _dense_two_site(pv, Am, Dm, step, eps, sh, trunc_tol, max_rank, bwd):
+    """the dense branch of `_step_size_local_solve` from the assembled pencil on: the eigensolve with its
+    speculative tail, then the split.  Returns (s1, s2, step, old_res)."""
+    k = min(sh[0] * sh[1], sh[2] * sh[3])
+    if _FUSED_TAIL and _trunc_kick_fits(sh, max_rank, bwd):
+        # the whole tail (ttk_trunc_kick) behind the eigensolve: ev, r, q and S come back in the one read.
+        # The kick block is drawn first; nothing else draws before the composed path's draw, so the
+        # stream is the same.  On ev < 0 the split is redone on the branch's solution with the same block.
+        G = _trunc_gauss(sh, bwd)
+        sol, step, old_res, pre = _dense_step(
+            pv, Am, Dm, step, eps, "two-site",
+            post=(4 + k, lambda v, info: D.trunc_kick(int(bwd), v.view(sh[0] * sh[1], sh[2] * sh[3]), G, trunc_tol,
+                                                      max_rank, 1, info_out=info), True))
+        if pre is not None:
+            return _trunc_views(*pre, sh) + (step, old_res)
+        return _trunc_split(sol, sh, trunc_tol, max_rank, bwd, 1, G) + (step, old_res)
+    sol, step, old_res, pre = _dense_step(
+        pv, Am, Dm, step, eps, "two-site",
+        post=(k, lambda v, S_out: _split_svd(_normalise(v), sh, bwd, S_out)) if _FUSED_TAIL else None)
+    if pre is not None:
+        s1, s2 = _split(None, sh, trunc_tol, max_rank, bwd, pre=pre)
+        return s1, s2, step, old_res
+    return _two_site_tail(sol, sh, trunc_tol, max_rank, bwd, step, old_res)
+
+
 def _step_size_local_solve(p1, p2, XAX_k, A_k, A_kp1, XAX_k2, XDX_k, D_k, D_kp1, XDX_k2, step, size_limit,
                            trunc_tol, eps, max_rank, bwd=True):
     """`_step_size_local_solve` (`src/tt_als.py:931-1038`): dense exact local eigensolve when
@@ -429,29 +489,19 @@ def _step_size_local_solve(p1, p2, XAX_k, A_k, A_kp1, XAX_k2, XDX_k, D_k, D_kp1,
     prev = einsum("rny,ytR->rntR", p1, p2)
     sh = tuple(prev.shape)
     m = int(np.prod(sh))
+    pv = prev.view(-1)
     if sh[0] * sh[-1] <= size_limit:
         _check_dense(m)
-        pv = prev.view(-1)
         with D.einsum_batch():  # the two assemblies are independent: grouped launches, same arithmetic
             Dr = einsum(TWO_SITE, XDX_k, D_k, D_kp1, XDX_k2)
             Ar = einsum(TWO_SITE, XAX_k, A_k, A_kp1, XAX_k2)
         Dm, Am = _sym(Dr, m), _sym(Ar, m)
-        k = min(sh[0] * sh[1], sh[2] * sh[3])
-        sol, step, old_res, pre = _dense_step(
-            pv, Am, Dm, step, eps, "two-site",
-            post=(k, lambda v, S_out: _split_svd(_normalise(v), sh, bwd, S_out)) if _FUSED_TAIL else None)
-        if pre is not None:
-            s1, s2 = _split(None, sh, trunc_tol, max_rank, bwd, pre=pre)
-            return s1, s2, step, old_res
-    else:
-        pv = prev.view(-1)
-        eq = "lsr,smnk,kptS,LSR,rntR->lmpL"
-        sol, step, old_res = _iterative_step(
-            pv, lambda v: einsum(eq, XAX_k, A_k, A_kp1, XAX_k2, v.view(*sh)).view(-1),
-            lambda v: einsum(eq, XDX_k, D_k, D_kp1, XDX_k2, v.view(*sh)).view(-1), step, eps, "two-site")
-    sol = _normalise(sol)
-    s1, s2 = _split(sol, sh, trunc_tol, max_rank, bwd)
-    return s1, s2, step, old_res
+        return _dense_two_site(pv, Am, Dm, step, eps, sh, trunc_tol, max_rank, bwd)
+    eq = "lsr,smnk,kptS,LSR,rntR->lmpL"
+    sol, step, old_res = _iterative_step(
+        pv, lambda v: einsum(eq, XAX_k, A_k, A_kp1, XAX_k2, v.view(*sh)).view(-1),
+        lambda v: einsum(eq, XDX_k, D_k, D_kp1, XDX_k2, v.view(*sh)).view(-1), step, eps, "two-site")
+    return _two_site_tail(sol, sh, trunc_tol, max_rank, bwd, step, old_res)
 
 
 def _step_size_local_solve_last(prev, XDX_k, Dk, XDX_k1, XAX_k, Ak, XAX_k1, dense, step, eps, post=None):
@@ -517,6 +567,10 @@ def _native_eig():
         if hasattr(L, "ttk_split_kick"):  # the 16th and 17th address (0 in the 15th: no ttk_svd_tol_read)
             addr += [0] * (15 - len(addr))
             addr += [ctypes.cast(f, ctypes.c_void_p).value for f in (L.ttk_split_kick_lds, L.ttk_split_kick)]
+        if hasattr(L, "ttk_trunc_kick"):  # the 18th to 20th address
+            addr += [0] * (17 - len(addr))
+            addr += [ctypes.cast(f, ctypes.c_void_p).value for f in (L.ttk_trunc_kick_lds, L.ttk_trunc_kick,
+                                                                     L.ttk_trunc_kick_read)]
         B.bind_eig(addr)
         _NATIVE_BOUND.append(True)
     D._stream()
@@ -547,7 +601,8 @@ def tt_max_generalised_eigen(A, Delta, x0=None, nswp=10, tol=1e-8, size_limit=25
         st = R.get_state()
         status, step, max_res, _, xs, key, pos, hg, g, why = B.eig_als(
             list(A), list(Delta), list(x), o3, int(nswp), float(tol), int(size_limit), float(tol / np.sqrt(d)),
-            int(np.floor(2 ** (d / 2))), MAX_DENSE, st[1], st[2], st[3], st[4], bool(D.SPLIT_KICK))
+            int(np.floor(2 ** (d / 2))), MAX_DENSE, st[1], st[2], st[3], st[4], bool(D.SPLIT_KICK),
+            bool(D.TRUNC_KICK))
         if status == 0:
             NATIVE_CALLS["native"] += 1
             R.set_state(("MT19937", key, pos, hg, g))

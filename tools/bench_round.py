@@ -51,6 +51,16 @@ and upload it inside the clock.
 
     python tools/bench_round.py kick [reps] [rounds]
 
+`trunc` times the whole tail of a two-site local solve (`tt_eig._two_site_tail`: normalise, truncation SVD, rank
+decision, kicked QR / RQ, product), by the same method, at (a, b) = (8, 8), (16, 16) and (64, 64) in both sweep
+directions, kick rank 4, on U diag(0.5^j) V^T with a threshold that keeps about half of the singular values.
+Three paths alternate in one run: today's default (`normalized`, `ttk_svd` with its read, the host's rank rule,
+the composed split), the same with TTIPM_SPLIT_KICK=1, and the one call `ttk_trunc_kick_read`
+(TTIPM_TRUNC_KICK=1: one launch, its info read in the call).  Every path draws the same Gaussian block on the
+host and uploads it inside the clock.
+
+    python tools/bench_round.py trunc [reps] [rounds]
+
 `many` times a group of independent roundings as one launch (`ttk_affine_round_many`, one workgroup per job, one
 host read for the group: `tt_ops.tt_affine_rank_reduce_many` under TTIPM_AFFINE_ROUND_MANY=1) against the same
 jobs as N `ttk_affine_round_one` calls in sequence on the same library (one launch and one host read each), by the
@@ -569,8 +579,85 @@ def main_kick(argv):
             bench_kick(a, b, r, bwd, reps, rounds)
 
 
+def bench_trunc(a, b, bwd, reps, rounds):
+    from ttipm_amd import tt_eig as E
+    rng = np.random.default_rng(5)
+    p = min(a, b)
+    U, _ = np.linalg.qr(rng.standard_normal((a, p)))
+    V, _ = np.linalg.qr(rng.standard_normal((b, p)))
+    s = 0.5 ** np.arange(p)
+    s /= np.linalg.norm(s)
+    sol = D.from_numpy((U * s) @ V.T)
+    sc = np.cumsum(s[::-1] ** 2)[::-1]
+    keep = p // 2
+    tol = float(np.sqrt(np.sqrt(sc[keep] * sc[keep - 1])))  # between the two tail sums: no near tie
+    sh = (a, 1, b, 1)
+    lds = D.lib.ttk_trunc_kick_lds(int(bwd), a, b, 4, p, None)
+    assert lds >= 0
+
+    def call(split_kick, trunc_kick):
+        def f():
+            D.SPLIT_KICK, D.TRUNC_KICK = split_kick, trunc_kick
+            return E._two_site_tail(sol, sh, tol, p, bwd, 1.0, None)[:2]
+        return f
+
+    what = (("composed tail (the default)", call(False, False)), ("TTIPM_SPLIT_KICK=1", call(True, False)),
+            ("ttk_trunc_kick_read", call(False, True)))
+    info = {}
+    ref = None
+    for name, f in what:
+        np.random.seed(7)
+        s1, s2 = f()
+        torch.cuda.synchronize()
+        l0, s0 = D.lib.ttk_launch_count(), D.lib.ttk_sync_count()
+        f()
+        torch.cuda.synchronize()
+        nl, ns = D.lib.ttk_launch_count() - l0, D.lib.ttk_sync_count() - s0
+        prod = D.read(s1).reshape(a, -1) @ D.read(s2).reshape(-1, b)
+        ref = prod if ref is None else ref
+        info[name] = (int(s1.shape[-1]), nl, ns, float(np.max(np.abs(prod - ref)) / np.max(np.abs(ref))))
+        for _ in range(20):  # warm-up of every shape the timed window uses
+            f()
+    torch.cuda.synchronize()
+    times = {name: [] for name, _ in what}
+    for _ in range(rounds):
+        for name, f in what:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                f()
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) / reps * 1e6)
+    D.SPLIT_KICK = D.TRUNC_KICK = False
+    print(f"{'backward' if bwd else 'forward'} tail a={a} b={b} kept {keep} of {p} kick 4; LDS {lds} bytes; {reps} calls x "
+          f"{rounds} rounds, us per call", flush=True)
+    for name, _ in what:
+        t = np.array(times[name])
+        q, nl, ns, err = info[name]
+        print(f"{name:30s} median {np.median(t):8.1f}  min {t.min():8.1f}  max {t.max():8.1f}  launches {nl:3d}  "
+              f"host waits {ns:2d}  |s1 s2 - default|/|default| {err:.2e}  rank {q}", flush=True)
+    old, mid, new = (np.array(times[name]) for name, _ in what)
+    for label, other in (("the composed tail", old), ("TTIPM_SPLIT_KICK=1", mid)):
+        spread = max(other.max() - other.min(), new.max() - new.min())
+        gap = float(np.median(other) - np.median(new))
+        print(f"ttk_trunc_kick_read: {np.median(other) / np.median(new):.2f}x {label} (medians {gap:.1f} us apart, "
+              f"min-max spread {spread:.1f} us: {'beyond' if abs(gap) > spread else 'within'} the spread)", flush=True)
+    print(flush=True)
+
+
+def main_trunc(argv):
+    reps = int(argv[0]) if argv else 100
+    rounds = int(argv[1]) if len(argv) > 1 else 7
+    assert torch.cuda.is_available(), "bench_round needs an MI355X"
+    for a, b in ((8, 8), (16, 16), (64, 64)):
+        for bwd in (False, True):
+            bench_trunc(a, b, bwd, reps, rounds)
+
+
 if __name__ == "__main__":
-    if sys.argv[1:2] == ["kick"]:
+    if sys.argv[1:2] == ["trunc"]:
+        main_trunc(sys.argv[2:])
+    elif sys.argv[1:2] == ["kick"]:
         main_kick(sys.argv[2:])
     elif sys.argv[1:2] == ["many"]:
         main_many(sys.argv[2:])
