@@ -274,6 +274,8 @@ def clone_many(srcs):
 
 def mul_(dst, a, b, alpha=1.0, beta=0.0):
     """dst = alpha * a * b + beta * dst (element-wise, same shapes, any strides)."""
+    if dst.dim() == 0:  # as copy_: a 0-d tensor is one element
+        dst, a, b = dst.reshape(1), a.reshape(1), b.reshape(1)
     f = _TL.fast or _fast()
     if f is not None:
         return f.mul_(dst, a, b, float(alpha), float(beta))

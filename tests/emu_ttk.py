@@ -28,6 +28,10 @@ def _i32(ptr, n):
     return np.ctypeslib.as_array((ctypes.c_int32 * int(n)).from_address(int(ptr)))
 
 
+MAXD = 6  # ttk::MAXD: more axes are TTK_ERR_ARG (csrc/ttk_contract.hip make_nd)
+ERR_ARG = 1
+
+
 def _nd_index(ndim, shape, strides):
     shape = [int(shape[i]) for i in range(ndim)]
     idx = np.zeros(shape, dtype=np.int64)
@@ -42,6 +46,12 @@ class EmuLib:
     def __init__(self):
         self.err = b""
         self.launches = 0
+
+    def _bad_nd(self, nd):
+        if 0 <= nd <= MAXD:
+            return False
+        self.err = b"ndim %d out of range (max %d)" % (nd, MAXD)
+        return True
 
     # --- bookkeeping
     def ttk_last_error(self):
@@ -119,6 +129,8 @@ class EmuLib:
     # --- element-wise
     def ttk_copy_nd(self, s, src, dst, nd, shape, ss, ds, alpha, beta):
         self.launches += 1
+        if self._bad_nd(nd):
+            return ERR_ARG
         i_s, i_d = _nd_index(nd, shape, ss), _nd_index(nd, shape, ds)
         if i_s.size == 0:
             return 0
@@ -132,6 +144,8 @@ class EmuLib:
 
     def ttk_mul_nd(self, s, a, b, dst, nd, shape, sa, sb, ds, alpha, beta):
         self.launches += 1
+        if self._bad_nd(nd):
+            return ERR_ARG
         ia, ib, idd = _nd_index(nd, shape, sa), _nd_index(nd, shape, sb), _nd_index(nd, shape, ds)
         if ia.size == 0:
             return 0
@@ -144,6 +158,11 @@ class EmuLib:
 
     def ttk_scale_axis(self, s, src, dst, nd, shape, ss, ds, axis, scales):
         self.launches += 1
+        if self._bad_nd(nd):
+            return ERR_ARG
+        if not 0 <= axis < nd or int(shape[axis]) > 16:
+            self.err = b"ttk_scale_axis: axis out of range (max extent 16)"
+            return ERR_ARG
         i_s, i_d = _nd_index(nd, shape, ss), _nd_index(nd, shape, ds)
         if i_s.size == 0:
             return 0
@@ -156,6 +175,8 @@ class EmuLib:
 
     def ttk_dot_nd_dev(self, s, x, y, nd, shape, xs, ys, out):
         self.launches += 1
+        if self._bad_nd(nd):
+            return ERR_ARG
         ix, iy = _nd_index(nd, shape, xs), _nd_index(nd, shape, ys)
         v = 0.0 if ix.size == 0 else float(np.dot(_dv(x, ix.max() + 1)[ix], _dv(y, iy.max() + 1)[iy]))
         _dv(out, 1)[0] = v
@@ -163,6 +184,9 @@ class EmuLib:
 
     def ttk_tt_join(self, s, a, b, out, ra, Ra, rb, Rb, mid, mode):
         self.launches += 1
+        if mode not in (0, 1, 2) or (mode == 1 and ra != rb) or (mode == 2 and Ra != Rb):
+            self.err = b"ttk_tt_join: bad mode / shapes"
+            return ERR_ARG
         A = _dv(a, ra * mid * Ra).reshape(ra, mid, Ra)
         B = _dv(b, rb * mid * Rb).reshape(rb, mid, Rb)
         if mode == 0:
@@ -178,6 +202,8 @@ class EmuLib:
 
     def ttk_axpby_nd(self, s, src, src2, dst, nd, shape, s1, s2, ds, alpha, beta, gamma):
         self.launches += 1
+        if self._bad_nd(nd):
+            return ERR_ARG
         i1, i2, idd = _nd_index(nd, shape, s1), _nd_index(nd, shape, s2), _nd_index(nd, shape, ds)
         if i1.size == 0:
             return 0
@@ -188,6 +214,11 @@ class EmuLib:
 
     def ttk_scale_axis_ss(self, s, src, dst, nd, shape, ss, ds, axis, sumsq, invert):
         self.launches += 1
+        if self._bad_nd(nd):
+            return ERR_ARG
+        if not 0 <= axis < nd:
+            self.err = b"ttk_scale_axis_ss: axis out of range"
+            return ERR_ARG
         i_s, i_d = _nd_index(nd, shape, ss), _nd_index(nd, shape, ds)
         if i_s.size == 0:
             return 0
@@ -204,12 +235,15 @@ class EmuLib:
 
     def ttk_normalize(self, s, x, out, nd, shape, xs):
         self.launches += 1
+        if self._bad_nd(nd):
+            return ERR_ARG
         ix = _nd_index(nd, shape, xs)
         if ix.size == 0:
             return 0
         v = _dv(x, ix.max() + 1)[ix].copy()
         d = float(np.dot(v, v))
-        _dv(out, ix.size)[:] = (1.0 / np.sqrt(0.0 if 0.0 > d else d)) * v
+        with np.errstate(divide="ignore", invalid="ignore"):  # the zero vector: inf / nan, as the kernel
+            _dv(out, ix.size)[:] = (1.0 / np.sqrt(np.float64(0.0 if 0.0 > d else d))) * v
         return 0
 
     def ttk_rayleigh_tail_sync(self, s, v, Mv, n, ev_out, r2_out):
@@ -229,6 +263,14 @@ class EmuLib:
         _dv(out2, 2)[:] = (ev, float(np.dot(b, b)))
         return 0
 
+    def ttk_copy_many(self, s, n, src, dst, count):
+        self.launches += 1
+        for j in range(n):
+            c = int(count[j])
+            if c > 0:
+                _dv(dst[j], c)[:] = _dv(src[j], c)
+        return 0
+
     def ttk_recip(self, s, src, dst, n):
         _dv(dst, n)[:] = 1.0 / _dv(src, n)
         return 0
@@ -243,6 +285,8 @@ class EmuLib:
         return 0
 
     def ttk_dot_nd_sync(self, s, x, y, nd, shape, xs, ys, out):
+        if self._bad_nd(nd):
+            return ERR_ARG
         ix, iy = _nd_index(nd, shape, xs), _nd_index(nd, shape, ys)
         val = float(np.dot(_dv(x, ix.max() + 1)[ix], _dv(y, iy.max() + 1)[iy])) if ix.size else 0.0
         out._obj.value = val
@@ -278,6 +322,9 @@ class EmuLib:
         return 0
 
     def ttk_sumsq_batched_strided(self, s, x, n, nb, bstride, inner, ostride, out):
+        if nb > 0 and inner <= 0:
+            self.err = b"ttk_sumsq_batched_strided: inner"
+            return ERR_ARG
         outer = n // inner
         xv = _dv(x, (nb - 1) * bstride + (outer - 1) * ostride + inner)
         o = _dv(out, nb)
